@@ -6,9 +6,11 @@ Contract (see the task's bench section): `python bench.py --gpus N --steps K --w
 8(d): V_b = V0 + 0.01 N(0,1), seed 20261015+b), inputs resident in HBM before the timed region.
 For N > 1 (torch.distributed.run, one process per GPU) every rank evaluates its own B instances
 (weak scaling, no data-path collective); the timed region is bracketed by barriers and the max
-over ranks is reported.  `value` = evaluations/s of the whole job.
+over ranks is reported.  `value` = evaluations/s of the whole job, `ms_per_step` the time of one
+timed step.  A plain run does this and nothing else; `--dump-outputs DIR` also writes what the last
+timed step computed as DIR/<name>.npy (dump_outputs), for comparing two builds output for output.
 
-Also reported:
+Also reported with `--full` (full_blocks; a plain run skips all of it):
   roofline     -- one evaluation = ap2_node_kernel (generated straight-line node Jacobians, one
                   thread per collocation node) + ap2_gather_kernel (J_g values, gradient): the
                   algorithmic HBM bytes per launch (SURVEY 8(d) formula with the exact nnz, x B) /
@@ -257,6 +259,13 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=2048, help="NLP instances per step and GPU")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (f, g, grad f, J_g) as "
+                         "DIR/<name>.npy (float64; see dump_outputs for the sampling of g, grad f and J_g)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline measurement also run every other block (roofline and per-kernel times, "
+                         "path A/B, configs 3-5, sweeps, Hessian, batch-1 latency, CPU baselines); the options below "
+                         "select among those blocks and have no effect without --full")
     ap.add_argument("--cpu-seconds", type=float, default=6.0, help="CPU baseline time per thread setting")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-hessian", action="store_true", help="skip the nlp_hess_l timing block")
@@ -352,6 +361,85 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    if args.dump_outputs:
+        # before any further launch: f, g, gr and jac hold what the last timed step wrote
+        dump_outputs(args.dump_outputs, {"f": f, "g": g, "grad_f": gr, "jac_g": jac}, rank)
+
+    line = None
+    if rank == 0:
+        line = {
+            "metric": "NLP f/g/Jacobian evals/sec, AP2 N=40 d=4",
+            "value": B * args.steps * world / elapsed,
+            "unit": "evals/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": elapsed / args.steps * 1e3,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f64",
+            "data": "synthetic (standard circular-orbit initial guess + 0.01 N(0,1), SURVEY 8(d))",
+            "config": {"workload": f"AP2 single kite, direct collocation radau N=40 d=4 zoh, "
+                                   f"{B} NLP instances per step and GPU, one eval = f + g + grad f + J_g",
+                       "n_v": lay.n_v, "n_g": lay.n_g, "nnz_jac": ev.nnz, "batch_per_gpu": B,
+                       "parallelism": f"replicas x{world}"},
+            "eval_path": ev.path,
+            "input_layout": input_layout,
+        }
+    if args.full:
+        full_blocks(args, line, ev, consts, lay, v0, V, P, f, g, gr, jac, step, B, dev, stream, dist, world, rank)
+    if rank == 0:
+        print(json.dumps(line))
+    if dist is not None:
+        dist.destroy_process_group()
+
+
+DUMP_BYTES = 56 << 20     # budget of one --dump-outputs directory (float64), under the 64 MB a dump may take
+DUMP_SEED = 20261019
+
+
+def dump_outputs(path, outputs, rank):
+    """Write the evaluation's outputs as path/<name>.npy (float64; <name>.rank<r>.npy for r > 0).
+    f is written whole.  g, grad f and J_g are [B, n] with B n far over the budget at the default
+    batch, so each is written as two fixed samples drawn from DUMP_SEED (the same for every run of
+    the same shapes): `<name>_rows` = a sorted sample of instances, every entry of each, and
+    `<name>_cols` = every instance at a sorted sample of 256 entries.  An output that fits is
+    written whole under its own name instead."""
+    import numpy as np
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    two_d = {k: t for k, t in outputs.items() if t.dim() == 2}
+    whole = sum(t.numel() for t in outputs.values()) * 8 <= DUMP_BYTES
+    arrays = {}
+    for name, t in outputs.items():
+        if whole or t.dim() != 2:
+            arrays[name] = t
+            continue
+        B, n = t.shape
+        ncols = min(n, 256)
+        per_instance = sum(x.shape[1] for x in two_d.values()) * 8
+        left = DUMP_BYTES - sum(B * min(x.shape[1], 256) for x in two_d.values()) * 8
+        nrows = max(1, min(B, left // per_instance))
+        rows = torch.as_tensor(np.sort(rng.choice(B, nrows, replace=False)), device=t.device)
+        cols = torch.as_tensor(np.sort(rng.choice(n, ncols, replace=False)), device=t.device)
+        arrays[name + "_rows"] = t[rows]
+        arrays[name + "_cols"] = t[:, cols]
+    suffix = "" if rank == 0 else f".rank{rank}"
+    for name, t in arrays.items():
+        np.save(os.path.join(path, f"{name}{suffix}.npy"), t.detach().to("cpu", torch.float64).contiguous().numpy())
+
+
+def full_blocks(args, line, ev, consts, lay, v0, V, P, f, g, gr, jac, step, B, dev, stream, dist, world, rank):
+    """Everything the benchmark reports beside its headline figure (--full): adds the blocks'
+    records to `line` on rank 0; every rank takes part in the blocks that span the job."""
+    import numpy as np
+    import torch
+
+    from awebox_amd import problem as pb
+
     # dominant-kernel duration from the HIP events the library records on the launch stream
     kms, fms, nms, gms, sms = [], [], [], [], []
     gen = ev.path == "generated"
@@ -388,42 +476,18 @@ def main():
     if args.dual_sweep_points > 0:
         dual_sweep = dual_sweep_block(args.dual_sweep_points, world, dist, dev, with_chain=not args.no_dual_chain)
     if rank != 0:
-        if dist is not None:
-            dist.destroy_process_group()
         return
 
-    evals = B * args.steps * world
-    value = evals / elapsed
     kernel_ms = float(np.mean(kms))
     bytes_per_eval = 8 * (lay.n_v + lay.n_v + pb.NTHETA0 + pb.NW + pb.NCOST + lay.n_g + lay.n_v + ev.nnz + 1)
     achieved = bytes_per_eval * B / (kernel_ms * 1e-3) / 1e9
-    line = {
-        "metric": "NLP f/g/Jacobian evals/sec, AP2 N=40 d=4",
-        "value": value,
-        "unit": "evals/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": elapsed / args.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic (standard circular-orbit initial guess + 0.01 N(0,1), SURVEY 8(d))",
-        "config": {"workload": f"AP2 single kite, direct collocation radau N=40 d=4 zoh, "
-                               f"{B} NLP instances per step and GPU, one eval = f + g + grad f + J_g",
-                   "n_v": lay.n_v, "n_g": lay.n_g, "nnz_jac": ev.nnz, "batch_per_gpu": B,
-                   "parallelism": f"replicas x{world}"},
-        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBS, "traffic": None,
-                     "kernel": ("ap2_soa_shoot + ap2_soa_radau + ap2_soa_interval + ap2_finalize "
-                                "(one evaluation, V and P instance-minor)"
-                                if soa else "ap2_node_kernel + ap2_gather_kernel" if gen else "ap2_interval_kernel"),
-                     "kernel_ms": kernel_ms, "finalize_ms": float(np.mean(fms)), "bytes_per_eval": bytes_per_eval},
-        "outputs_finite": finite,
-        "eval_path": ev.path,
-        "input_layout": input_layout,
-    }
+    line["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": achieved / HBM_PEAK_GBS, "traffic": None,
+                        "kernel": ("ap2_soa_shoot + ap2_soa_radau + ap2_soa_interval + ap2_finalize "
+                                   "(one evaluation, V and P instance-minor)"
+                                   if soa else "ap2_node_kernel + ap2_gather_kernel" if gen else "ap2_interval_kernel"),
+                        "kernel_ms": kernel_ms, "finalize_ms": float(np.mean(fms)), "bytes_per_eval": bytes_per_eval}
+    line["outputs_finite"] = finite
     if gen:
         line["roofline"]["kernels"] = gen_kernels(ev, lay, B, float(np.mean(nms)), float(np.mean(gms)))
     if soa:
@@ -486,11 +550,7 @@ def main():
         line["latency_batch1"] = latency_block(consts, lay, v0, with_cpu=not args.no_cpu_baseline)
     if world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(consts, lay, v0, args.cpu_seconds)
-    if rank == 0:
-        line["casadi_probe"] = casadi_probe()
-    print(json.dumps(line))
-    if dist is not None:
-        dist.destroy_process_group()
+    line["casadi_probe"] = casadi_probe()
 
 
 def dual_block(B, rank, dev, dist, world, steps=20, warmup=3, cpu_seconds=0.0):

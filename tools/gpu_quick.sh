@@ -12,7 +12,7 @@ step() {  # step <limit> <log> <cmd...>
     if [ $rc -ne 0 ]; then exit $rc; fi
 }
 step 400 pytest_parity.log python -u -m pytest -x -q --timeout 300 --timeout-method thread tests/test_gpu_parity.py tests/test_gen_path_gpu.py -m gpu
-step 300 bench_ap2.log python -u bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-hessian --no-latency \
+step 300 bench_ap2.log python -u bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-hessian --no-latency \
     --mpc-batch 0 --pmpc-loops 0 --dual-batch 0 --dual-sweep-points 0 --sweep-points 0
 if [ "${1:-}" = "ens" ]; then
     step 400 ens_gen.log python -u tools/final_step_ensemble.py --path generated --k 16 --eps 1e-13 --trace gpurun_out/ens_trace_gen.json

@@ -4,7 +4,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 set -o pipefail
 O=gpurun_out/bench6
 mkdir -p $O
-timeout -k 10 700 python -u bench.py > $O/bench.log 2>&1 || { tail -30 $O/bench.log; exit 1; }
+timeout -k 10 700 python -u bench.py --full > $O/bench.log 2>&1 || { tail -30 $O/bench.log; exit 1; }
 grep '^{' $O/bench.log | python -c "
 import json,sys
 d=json.loads(sys.stdin.readline())

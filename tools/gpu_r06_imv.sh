@@ -12,6 +12,6 @@ step() {  # step <limit> <log> <cmd...>
     if [ $rc -ne 0 ]; then exit $rc; fi
 }
 step 300 imv_test.log python -u -m pytest -x -v --timeout 200 --timeout-method thread tests/test_gen_path_gpu.py tests/test_gpu_parity.py
-step 300 bench_ap2.log python -u bench.py --steps 20 --warmup 3 --no-hessian --no-latency --no-cpu-baseline --mpc-batch 0 --dual-batch 0 --sweep-points 0 --dual-sweep-points 0
+step 300 bench_ap2.log python -u bench.py --full --steps 20 --warmup 3 --no-hessian --no-latency --no-cpu-baseline --mpc-batch 0 --dual-batch 0 --sweep-points 0 --dual-sweep-points 0
 bash tools/gpu_pmc_soa.sh || exit $?
 echo R06_IMV_DONE

@@ -7,7 +7,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
 run() {  # run <tag> <env...>
     local tag=$1; shift
-    timeout -k 10 400 env "$@" python -u bench.py --steps 5 --warmup 2 --batch 256 --no-cpu-baseline --no-hessian \
+    timeout -k 10 400 env "$@" python -u bench.py --full --steps 5 --warmup 2 --batch 256 --no-cpu-baseline --no-hessian \
         --no-latency --mpc-batch 32 --dual-batch 0 > "gpurun_out/solver_ab_$tag.log" 2>&1 || exit $?
     python - "$tag" <<'PY'
 import json, sys

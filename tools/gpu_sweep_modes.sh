@@ -6,7 +6,7 @@
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
 for mode in fan batch chain fan batch; do
-    timeout -k 10 300 python -u bench.py --steps 2 --warmup 1 --batch 256 --no-cpu-baseline --no-hessian --no-latency \
+    timeout -k 10 300 python -u bench.py --full --steps 2 --warmup 1 --batch 256 --no-cpu-baseline --no-hessian --no-latency \
         --mpc-batch 0 --dual-batch 0 --dual-sweep-points 0 --sweep-mode $mode > gpurun_out/sweep_mode_$mode.log 2>&1 || exit $?
     python -c "
 import json,sys
