@@ -27,11 +27,13 @@
 
 #include <cmath>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "../../include/awedual.h"
 #include "../../include/awegpu.h"
+#include "host_util.hpp"
 #include "dual_model.hpp"
 #include "dual_tables.hpp"
 #include "dual_hess_tables.hpp"
@@ -40,21 +42,7 @@
 namespace {
 
 using namespace dlt;
-
-thread_local std::string g_err;
-
-int fail(int code, const std::string& msg) {
-    g_err = msg;
-    return code;
-}
-
-#define ADL_TRY(expr)                                                                  \
-    do {                                                                               \
-        hipError_t _e = (expr);                                                        \
-        if (_e != hipSuccess)                                                          \
-            return fail(AWE_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-    } while (0)
-
+using namespace hostu;
 
 struct DArgs {
     const double* V;
@@ -944,7 +932,7 @@ __global__ __launch_bounds__(64) void dual_hess_finalize_kernel(HDArgs ha) {
 template <int D>
 int launch_hess(const HDArgs& ha, int batch, size_t dyn, hipStream_t s) {
     // the LDS image (tangents + direction-pair Hessian) exceeds 64 KiB: raise the dynamic limit
-    ADL_TRY(hipFuncSetAttribute((const void*)dual_hess_kernel<D>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
+    HIP_TRY(hipFuncSetAttribute((const void*)dual_hess_kernel<D>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
     dual_hess_kernel<D><<<dim3((unsigned)(batch * ha.a.n_k)), kBlock, dyn, s>>>(ha);
     return 0;
 }
@@ -961,30 +949,30 @@ struct adl_handle_s {
     Tables t;
     int batch = 0;
     std::vector<double> consts;
-    double* d_cst = nullptr;
-    ColorTabs* d_ct = nullptr;
-    int* d_goff = nullptr;
-    int* d_gslot = nullptr;
-    uint32_t* d_gcode = nullptr;
-    double* d_part = nullptr;
-    double *d_V = nullptr, *d_P = nullptr, *d_f = nullptr, *d_g = nullptr, *d_grad = nullptr, *d_jac = nullptr;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    DevBuf<double> d_cst;
+    DevBuf<ColorTabs> d_ct;
+    DevBuf<int> d_goff, d_gslot;
+    DevBuf<uint32_t> d_gcode;
+    DevBuf<double> d_part;
+    DevBuf<double> d_V, d_P, d_f, d_g, d_grad, d_jac, d_sigma, d_lam, d_H;   // staging of the host entry points
+    Event ev[3];
     bool timed = false;
-    // Hessian (built on first use)
-    DualHessTables* ht = nullptr;
-    DHessTabs* d_ht = nullptr;
-    int *d_tasks = nullptr, *d_ent_off = nullptr, *d_term_off = nullptr, *d_slot0 = nullptr, *d_nslot = nullptr;
-    int *d_hgslot = nullptr, *d_gcol = nullptr, *d_grow = nullptr;
-    short* d_task_target = nullptr;
-    unsigned* d_terms = nullptr;
-    double *d_gpart = nullptr, *d_apart = nullptr;
-    double *d_hV = nullptr, *d_hP = nullptr, *d_sigma = nullptr, *d_lam = nullptr, *d_H = nullptr;   // host-entry scratch
+    // Hessian (built on first use; ht is set once everything below it is uploaded)
+    std::unique_ptr<DualHessTables> ht;
+    DevBuf<DHessTabs> d_ht;
+    DevBuf<int> d_tasks, d_ent_off, d_term_off, d_slot0, d_nslot, d_hgslot, d_gcol, d_grow;
+    DevBuf<short> d_task_target;
+    DevBuf<unsigned> d_terms;
+    DevBuf<double> d_gpart, d_apart;
     int hd_total = 0;
     size_t hess_dyn = 0;
-    hipEvent_t hev[2] = {nullptr, nullptr};
+    Event hev[2];
     bool htimed = false;
     // generated instance-minor path (adl_eval_nlp_im, awedual_gen.hip)
-    dgen::Plan* gen = nullptr;
+    struct PlanDelete {
+        void operator()(dgen::Plan* p) const { dgen::destroy(p); }
+    };
+    std::unique_ptr<dgen::Plan, PlanDelete> gen;
     std::string gen_why;
 };
 
@@ -1019,39 +1007,30 @@ static size_t hess_dyn_fixed(int d) {
 // builds and uploads the Hessian tables on first use
 static int ensure_hess(adl_handle h) {
     if (h->ht) return AWE_OK;
-    auto* H = new DualHessTables();
+    auto H = std::make_unique<DualHessTables>();
     std::string err;
-    if (build_dual_hess_tables(h->t, h->consts.data(), *H, err)) {
-        delete H;
-        return fail(AWE_ERR_ARG, err);
-    }
+    if (build_dual_hess_tables(h->t, h->consts.data(), *H, err)) return fail(AWE_ERR_ARG, err);
     const Tables& T = h->t;
     h->hd_total = H->ht.npairs[0] + T.lay.d * H->ht.npairs[1];
     h->hess_dyn = sizeof(double) * ((size_t)T.tang_total + h->hd_total + hess_dyn_fixed(T.lay.d));
-    if (h->hess_dyn > 110 * 1024) {
-        delete H;
+    if (h->hess_dyn > 110 * 1024)
         return fail(AWE_ERR_ARG, "internal: Hessian LDS image exceeds the workgroup budget");
-    }
-    h->ht = H;
     const size_t nb = (size_t)h->batch, ng = H->gslot.size();
-#define ADL_UPLOAD(dst, src, n)                                                      \
-    ADL_TRY(hipMalloc((void**)&dst, sizeof(*dst) * (n)));                            \
-    ADL_TRY(hipMemcpy(dst, src, sizeof(*dst) * (n), hipMemcpyHostToDevice));
-    ADL_UPLOAD(h->d_ht, &H->ht, 1);
-    ADL_UPLOAD(h->d_tasks, H->tasks.data(), H->tasks.size());
-    ADL_UPLOAD(h->d_task_target, H->task_target.data(), H->task_target.size());
-    ADL_UPLOAD(h->d_ent_off, H->ent_off.data(), H->ent_off.size());
-    ADL_UPLOAD(h->d_term_off, H->term_off.data(), H->term_off.size());
-    ADL_UPLOAD(h->d_terms, H->terms.data(), H->terms.size());
-    ADL_UPLOAD(h->d_slot0, H->slot0.data(), H->slot0.size());
-    ADL_UPLOAD(h->d_nslot, H->nslot.data(), H->nslot.size());
-    ADL_UPLOAD(h->d_hgslot, H->gslot.data(), ng);
-    ADL_UPLOAD(h->d_gcol, H->gcol.data(), ng);
-    ADL_UPLOAD(h->d_grow, H->grow.data(), ng);
-#undef ADL_UPLOAD
-    ADL_TRY(hipMalloc((void**)&h->d_gpart, sizeof(double) * nb * T.lay.n_k * std::max<size_t>(ng, 1)));
-    ADL_TRY(hipMalloc((void**)&h->d_apart, sizeof(double) * nb * T.lay.n_k));
-    for (auto& e : h->hev) ADL_TRY(hipEventCreate(&e));
+    HIP_TRY(h->d_ht.upload(&H->ht, 1));
+    HIP_TRY(h->d_tasks.upload(H->tasks));
+    HIP_TRY(h->d_task_target.upload(H->task_target));
+    HIP_TRY(h->d_ent_off.upload(H->ent_off));
+    HIP_TRY(h->d_term_off.upload(H->term_off));
+    HIP_TRY(h->d_terms.upload(H->terms));
+    HIP_TRY(h->d_slot0.upload(H->slot0));
+    HIP_TRY(h->d_nslot.upload(H->nslot));
+    HIP_TRY(h->d_hgslot.upload(H->gslot.data(), ng));
+    HIP_TRY(h->d_gcol.upload(H->gcol.data(), ng));
+    HIP_TRY(h->d_grow.upload(H->grow.data(), ng));
+    HIP_TRY(h->d_gpart.alloc(nb * T.lay.n_k * std::max<size_t>(ng, 1)));
+    HIP_TRY(h->d_apart.alloc(nb * T.lay.n_k));
+    for (auto& e : h->hev) HIP_TRY(e.create());
+    h->ht = std::move(H);
     return AWE_OK;
 }
 
@@ -1066,7 +1045,7 @@ static int launch_hess_all(adl_handle h, const double* V, const double* P, const
     ha.sigma = sigma; ha.lam = lam; ha.H = Hv; ha.gpart = h->d_gpart; ha.apart = h->d_apart;
     ha.hnnz = H.nnz; ha.ng = (int)H.gslot.size(); ha.hd_total = h->hd_total;
     int rc = 0;
-    ADL_TRY(hipEventRecord(h->hev[0], s));
+    HIP_TRY(hipEventRecord(h->hev[0], s));
     switch (h->t.lay.d) {
         case 2: rc = launch_hess<2>(ha, h->batch, h->hess_dyn, s); break;
         case 3: rc = launch_hess<3>(ha, h->batch, h->hess_dyn, s); break;
@@ -1075,10 +1054,10 @@ static int launch_hess_all(adl_handle h, const double* V, const double* P, const
         default: return fail(AWE_ERR_ARG, "unsupported d");
     }
     if (rc) return rc;
-    ADL_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     dual_hess_finalize_kernel<<<dim3((unsigned)h->batch), 64, 0, s>>>(ha);
-    ADL_TRY(hipGetLastError());
-    ADL_TRY(hipEventRecord(h->hev[1], s));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(h->hev[1], s));
     h->htimed = true;
     return AWE_OK;
 }
@@ -1092,9 +1071,7 @@ int adl_sparsity_jac_static(int n_k, int d, const double* consts, int n_consts, 
     Tables T;
     std::string err;
     if (build_tables(n_k, d, consts, n_consts, T, err)) return fail(AWE_ERR_ARG, err);
-    *nnz = (int)T.row.size();
-    if (colind) std::memcpy(colind, T.colind.data(), sizeof(int) * T.colind.size());
-    if (row) std::memcpy(row, T.row.data(), sizeof(int) * T.row.size());
+    copy_ccs(nnz, colind, row, T.colind, T.row);
     return AWE_OK;
 }
 
@@ -1146,62 +1123,34 @@ int adl_create(int n_k, int d, const double* consts, int n_consts, int batch, ad
     if (d < 2 || d > 5) return fail(AWE_ERR_ARG, "the dual-kite kernel is instantiated for 2 <= d <= 5");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(AWE_ERR_NODEVICE, "no HIP device");
-    auto* h = new adl_handle_s();
+    auto h = std::make_unique<adl_handle_s>();   // freed, with all it owns, by every early return
     std::string err;
-    if (build_tables(n_k, d, consts, n_consts, h->t, err)) {
-        delete h;
-        return fail(AWE_ERR_ARG, err);
-    }
+    if (build_tables(n_k, d, consts, n_consts, h->t, err)) return fail(AWE_ERR_ARG, err);
     const Tables& T = h->t;
-    if (T.ct.ncol[0] + d * T.ct.ncol[1] > kBlock) {
-        delete h;
+    if (T.ct.ncol[0] + d * T.ct.ncol[1] > kBlock)
         return fail(AWE_ERR_ARG, "more (node, colour) tasks than threads per workgroup");
-    }
-    if ((int)consts[ADL_C_N_ELEMENTS] > kMaxElements) {
-        delete h;
+    if ((int)consts[ADL_C_N_ELEMENTS] > kMaxElements)
         return fail(AWE_ERR_ARG, "the dual-kite kernel supports at most 8 tether elements per segment");
-    }
-    if (T.gslot.size() >= (1u << 31) || T.tang_total >= (1 << 21)) {
-        delete h;
+    if (T.gslot.size() >= (1u << 31) || T.tang_total >= (1 << 21))
         return fail(AWE_ERR_ARG, "tables exceed the gather-code range");
-    }
     h->batch = batch;
     h->consts.assign(consts, consts + n_consts);
-#define ADL_UPLOAD(dst, src, n)                                                      \
-    ADL_TRY(hipMalloc((void**)&dst, sizeof(*dst) * (n)));                            \
-    ADL_TRY(hipMemcpy(dst, src, sizeof(*dst) * (n), hipMemcpyHostToDevice));
-    ADL_UPLOAD(h->d_cst, consts, n_consts);
-    ADL_UPLOAD(h->d_ct, &T.ct, 1);
-    ADL_UPLOAD(h->d_goff, T.goff.data(), T.goff.size());
-    ADL_UPLOAD(h->d_gslot, T.gslot.data(), T.gslot.size());
-    ADL_UPLOAD(h->d_gcode, T.gcode.data(), T.gcode.size());
-#undef ADL_UPLOAD
-    ADL_TRY(hipMalloc((void**)&h->d_part, sizeof(double) * (size_t)batch * n_k * kNPart));
-    for (auto& e : h->ev) ADL_TRY(hipEventCreate(&e));
-    if (int rc = dgen::create(T, h->consts, batch, &h->gen, h->gen_why, err)) {
-        adl_destroy(h);
-        return fail(rc, err);
-    }
-    *out = h;
+    HIP_TRY(h->d_cst.upload(consts, n_consts));
+    HIP_TRY(h->d_ct.upload(&T.ct, 1));
+    HIP_TRY(h->d_goff.upload(T.goff));
+    HIP_TRY(h->d_gslot.upload(T.gslot));
+    HIP_TRY(h->d_gcode.upload(T.gcode));
+    HIP_TRY(h->d_part.alloc((size_t)batch * n_k * kNPart));
+    for (auto& e : h->ev) HIP_TRY(e.create());
+    dgen::Plan* gen = nullptr;
+    if (int rc = dgen::create(T, h->consts, batch, &gen, h->gen_why, err)) return fail(rc, err);
+    h->gen.reset(gen);
+    *out = h.release();
     return AWE_OK;
 }
 
 int adl_destroy(adl_handle h) {
-    if (!h) return AWE_OK;
-    void* bufs[] = {h->d_cst, h->d_ct, h->d_goff, h->d_gslot, h->d_gcode, h->d_part,
-                    h->d_V, h->d_P, h->d_f, h->d_g, h->d_grad, h->d_jac,
-                    h->d_ht, h->d_tasks, h->d_ent_off, h->d_term_off, h->d_slot0, h->d_nslot, h->d_hgslot,
-                    h->d_gcol, h->d_grow, h->d_task_target, h->d_terms, h->d_gpart, h->d_apart,
-                    h->d_hV, h->d_hP, h->d_sigma, h->d_lam, h->d_H};
-    for (void* p : bufs)
-        if (p) (void)hipFree(p);
-    for (auto& e : h->ev)
-        if (e) (void)hipEventDestroy(e);
-    for (auto& e : h->hev)
-        if (e) (void)hipEventDestroy(e);
-    delete h->ht;
-    dgen::destroy(h->gen);
-    delete h;
+    delete h;   // the members free their device memory, events and the generated path's plan
     return AWE_OK;
 }
 
@@ -1217,7 +1166,7 @@ int adl_eval_nlp_im(adl_handle h, const double* V, const double* P, double* f, d
     if (!h || !V || !P || !f || !g || !grad_f || !jac) return fail(AWE_ERR_ARG, "null argument");
     if (!h->gen) return fail(AWE_ERR_ARG, "generated path unavailable: " + h->gen_why);
     std::string err;
-    if (int rc = dgen::eval(h->gen, h->d_cst, V, P, f, g, grad_f, jac, ld, (hipStream_t)stream, err))
+    if (int rc = dgen::eval(h->gen.get(), h->d_cst, V, P, f, g, grad_f, jac, ld, (hipStream_t)stream, err))
         return fail(rc, err);
     return AWE_OK;
 }
@@ -1226,7 +1175,7 @@ int adl_last_kernel_ms_im(adl_handle h, float* ms_in, float* ms_node, float* ms_
     if (!h || !h->gen) return fail(AWE_ERR_ARG, "no generated path");
     float ms[4];
     std::string err;
-    if (int rc = dgen::last_ms(h->gen, ms, err)) return fail(rc, err);
+    if (int rc = dgen::last_ms(h->gen.get(), ms, err)) return fail(rc, err);
     if (ms_in) *ms_in = ms[0];
     if (ms_node) *ms_node = ms[1];
     if (ms_interval) *ms_interval = ms[2];
@@ -1245,8 +1194,7 @@ int adl_sizes(adl_handle h, int* n_v, int* n_g, int* n_p, int* nnz) {
 
 int adl_sparsity_jac(adl_handle h, int* colind, int* row) {
     if (!h || !colind || !row) return fail(AWE_ERR_ARG, "null argument");
-    std::memcpy(colind, h->t.colind.data(), sizeof(int) * h->t.colind.size());
-    std::memcpy(row, h->t.row.data(), sizeof(int) * h->t.row.size());
+    copy_ccs(nullptr, colind, row, h->t.colind, h->t.row);
     return AWE_OK;
 }
 
@@ -1259,7 +1207,7 @@ int adl_eval_nlp(adl_handle h, const double* V, const double* P, double* f, doub
     DArgs a = make_args(h, V, P);
     a.f = f; a.g = g; a.grad = grad_f; a.jac = jac;
     const size_t dyn = sizeof(double) * (size_t)T.tang_total;
-    ADL_TRY(hipEventRecord(h->ev[0], s));
+    HIP_TRY(hipEventRecord(h->ev[0], s));
     switch (L.d) {
         case 2: launch<2>(a, h->batch, dyn, s); break;
         case 3: launch<3>(a, h->batch, dyn, s); break;
@@ -1267,20 +1215,20 @@ int adl_eval_nlp(adl_handle h, const double* V, const double* P, double* f, doub
         case 5: launch<5>(a, h->batch, dyn, s); break;
         default: return fail(AWE_ERR_ARG, "unsupported d");
     }
-    ADL_TRY(hipGetLastError());
-    ADL_TRY(hipEventRecord(h->ev[1], s));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(h->ev[1], s));
     dual_finalize_kernel<<<dim3((unsigned)h->batch), 64, 0, s>>>(a);
-    ADL_TRY(hipGetLastError());
-    ADL_TRY(hipEventRecord(h->ev[2], s));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(h->ev[2], s));
     h->timed = true;
     return AWE_OK;
 }
 
 int adl_last_kernel_ms(adl_handle h, float* ms_main, float* ms_fin) {
     if (!h || !h->timed) return fail(AWE_ERR_ARG, "no timed evaluation yet");
-    ADL_TRY(hipEventSynchronize(h->ev[2]));
-    if (ms_main) ADL_TRY(hipEventElapsedTime(ms_main, h->ev[0], h->ev[1]));
-    if (ms_fin) ADL_TRY(hipEventElapsedTime(ms_fin, h->ev[1], h->ev[2]));
+    HIP_TRY(hipEventSynchronize(h->ev[2]));
+    if (ms_main) HIP_TRY(hipEventElapsedTime(ms_main, h->ev[0], h->ev[1]));
+    if (ms_fin) HIP_TRY(hipEventElapsedTime(ms_fin, h->ev[1], h->ev[2]));
     return AWE_OK;
 }
 
@@ -1289,31 +1237,11 @@ int adl_eval_nlp_host(adl_handle h, const double* V, const double* P, double* f,
     if (!h || !V || !P || !f || !g || !grad_f || !jac) return fail(AWE_ERR_ARG, "null argument");
     const Layout& L = h->t.lay;
     const size_t nb = (size_t)h->batch, nnz = h->t.row.size();
-    if (!h->d_V) {
-        ADL_TRY(hipMalloc((void**)&h->d_V, sizeof(double) * nb * L.n_v));
-        ADL_TRY(hipMalloc((void**)&h->d_P, sizeof(double) * nb * L.n_p));
-        ADL_TRY(hipMalloc((void**)&h->d_f, sizeof(double) * nb));
-        ADL_TRY(hipMalloc((void**)&h->d_g, sizeof(double) * nb * L.n_g));
-        ADL_TRY(hipMalloc((void**)&h->d_grad, sizeof(double) * nb * L.n_v));
-        ADL_TRY(hipMalloc((void**)&h->d_jac, sizeof(double) * nb * nnz));
-    }
-    ADL_TRY(hipMemcpy(h->d_V, V, sizeof(double) * nb * L.n_v, hipMemcpyHostToDevice));
-    ADL_TRY(hipMemcpy(h->d_P, P, sizeof(double) * nb * L.n_p, hipMemcpyHostToDevice));
-    int rc = adl_eval_nlp(h, h->d_V, h->d_P, h->d_f, h->d_g, h->d_grad, h->d_jac, nullptr);
-    if (rc) return rc;
-    ADL_TRY(hipDeviceSynchronize());
-    ADL_TRY(hipMemcpy(f, h->d_f, sizeof(double) * nb, hipMemcpyDeviceToHost));
-    ADL_TRY(hipMemcpy(g, h->d_g, sizeof(double) * nb * L.n_g, hipMemcpyDeviceToHost));
-    ADL_TRY(hipMemcpy(grad_f, h->d_grad, sizeof(double) * nb * L.n_v, hipMemcpyDeviceToHost));
-    ADL_TRY(hipMemcpy(jac, h->d_jac, sizeof(double) * nb * nnz, hipMemcpyDeviceToHost));
-    auto finite = [](const double* x, size_t n) {
-        for (size_t i = 0; i < n; ++i)
-            if (!std::isfinite(x[i])) return false;
-        return true;
-    };
-    if (!finite(f, nb) || !finite(g, nb * L.n_g) || !finite(grad_f, nb * L.n_v) || !finite(jac, nb * nnz))
-        return fail(AWE_ERR_NONFINITE, "non-finite output");
-    return AWE_OK;
+    return host_round_trip(
+        {{h->d_V, V, nb * L.n_v}, {h->d_P, P, nb * L.n_p}},
+        {{h->d_f, f, nb}, {h->d_g, g, nb * L.n_g}, {h->d_grad, grad_f, nb * L.n_v}, {h->d_jac, jac, nb * nnz}},
+        [&] { return adl_eval_nlp(h, h->d_V, h->d_P, h->d_f, h->d_g, h->d_grad, h->d_jac, nullptr); },
+        "non-finite output");
 }
 
 int adl_hess_nnz(adl_handle h, int* nnz_h) {
@@ -1328,8 +1256,7 @@ int adl_sparsity_hess(adl_handle h, int* colind, int* row) {
     if (!h || !colind || !row) return fail(AWE_ERR_ARG, "null argument");
     int rc = ensure_hess(h);
     if (rc) return rc;
-    std::memcpy(colind, h->ht->colind.data(), sizeof(int) * h->ht->colind.size());
-    std::memcpy(row, h->ht->row.data(), sizeof(int) * h->ht->row.size());
+    copy_ccs(nullptr, colind, row, h->ht->colind, h->ht->row);
     return AWE_OK;
 }
 
@@ -1338,15 +1265,9 @@ int adl_sparsity_hess_static(int n_k, int d, const double* consts, int n_consts,
     Tables T;
     std::string err;
     if (build_tables(n_k, d, consts, n_consts, T, err)) return fail(AWE_ERR_ARG, err);
-    auto* H = new DualHessTables();
-    if (build_dual_hess_tables(T, consts, *H, err)) {
-        delete H;
-        return fail(AWE_ERR_ARG, err);
-    }
-    *nnz = H->nnz;
-    if (colind) std::memcpy(colind, H->colind.data(), sizeof(int) * H->colind.size());
-    if (row) std::memcpy(row, H->row.data(), sizeof(int) * H->row.size());
-    delete H;
+    auto H = std::make_unique<DualHessTables>();
+    if (build_dual_hess_tables(T, consts, *H, err)) return fail(AWE_ERR_ARG, err);
+    copy_ccs(nnz, colind, row, H->colind, H->row);
     return AWE_OK;
 }
 
@@ -1365,30 +1286,17 @@ int adl_eval_hess_host(adl_handle h, const double* V, const double* P, const dou
     if (rc) return rc;
     const Layout& L = h->t.lay;
     const size_t nb = (size_t)h->batch, hn = (size_t)h->ht->nnz;
-    if (!h->d_H) {
-        ADL_TRY(hipMalloc((void**)&h->d_hV, sizeof(double) * nb * L.n_v));
-        ADL_TRY(hipMalloc((void**)&h->d_hP, sizeof(double) * nb * L.n_p));
-        ADL_TRY(hipMalloc((void**)&h->d_sigma, sizeof(double) * nb));
-        ADL_TRY(hipMalloc((void**)&h->d_lam, sizeof(double) * nb * L.n_g));
-        ADL_TRY(hipMalloc((void**)&h->d_H, sizeof(double) * nb * hn));
-    }
-    ADL_TRY(hipMemcpy(h->d_hV, V, sizeof(double) * nb * L.n_v, hipMemcpyHostToDevice));
-    ADL_TRY(hipMemcpy(h->d_hP, P, sizeof(double) * nb * L.n_p, hipMemcpyHostToDevice));
-    ADL_TRY(hipMemcpy(h->d_sigma, sigma, sizeof(double) * nb, hipMemcpyHostToDevice));
-    ADL_TRY(hipMemcpy(h->d_lam, lam_g, sizeof(double) * nb * L.n_g, hipMemcpyHostToDevice));
-    rc = launch_hess_all(h, h->d_hV, h->d_hP, h->d_sigma, h->d_lam, h->d_H, nullptr);
-    if (rc) return rc;
-    ADL_TRY(hipDeviceSynchronize());
-    ADL_TRY(hipMemcpy(H, h->d_H, sizeof(double) * nb * hn, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < nb * hn; ++i)
-        if (!std::isfinite(H[i])) return fail(AWE_ERR_NONFINITE, "non-finite value in the Hessian");
-    return AWE_OK;
+    return host_round_trip(
+        {{h->d_V, V, nb * L.n_v}, {h->d_P, P, nb * L.n_p}, {h->d_sigma, sigma, nb}, {h->d_lam, lam_g, nb * L.n_g}},
+        {{h->d_H, H, nb * hn}},
+        [&] { return launch_hess_all(h, h->d_V, h->d_P, h->d_sigma, h->d_lam, h->d_H, nullptr); },
+        "non-finite value in the Hessian");
 }
 
 int adl_last_hess_ms(adl_handle h, float* ms) {
     if (!h || !h->htimed || !ms) return fail(AWE_ERR_ARG, "no timed Hessian launch yet");
-    ADL_TRY(hipEventSynchronize(h->hev[1]));
-    ADL_TRY(hipEventElapsedTime(ms, h->hev[0], h->hev[1]));
+    HIP_TRY(hipEventSynchronize(h->hev[1]));
+    HIP_TRY(hipEventElapsedTime(ms, h->hev[0], h->hev[1]));
     return AWE_OK;
 }
 

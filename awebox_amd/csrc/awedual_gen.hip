@@ -26,6 +26,7 @@
 
 #include <algorithm>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -34,6 +35,7 @@
 #include "../../include/awegpu.h"
 #include "awedual_gen.hpp"
 #include "dual_nodejac.gen.hpp"
+#include "host_util.hpp"
 #include "dual_tables.hpp"
 #include "im_layout.hpp"
 
@@ -601,22 +603,14 @@ struct Plan {
     Args a{};
     int d = 0;
     size_t ld = 0, nnz = 0;
-    unsigned *d_dtab = nullptr, *d_ctab = nullptr;
-    int* d_coff = nullptr;
-    double *d_VT = nullptr, *d_PT = nullptr, *d_objb = nullptr, *d_part = nullptr;
-    hipEvent_t ev[5] = {};
+    hostu::DevBuf<unsigned> d_dtab, d_ctab;
+    hostu::DevBuf<int> d_coff;
+    hostu::DevBuf<double> d_VT, d_PT, d_objb, d_part;
+    hostu::Event ev[5];
     bool timed = false;
 };
 
-void destroy(Plan* p) {
-    if (!p) return;
-    for (void* q : {(void*)p->d_dtab, (void*)p->d_ctab, (void*)p->d_coff, (void*)p->d_VT, (void*)p->d_PT,
-                    (void*)p->d_objb, (void*)p->d_part})
-        if (q) (void)hipFree(q);
-    for (auto& e : p->ev)
-        if (e) (void)hipEventDestroy(e);
-    delete p;
-}
+void destroy(Plan* p) { delete p; }
 
 // destination tables from the gather list of build_tables: per (interval k, node n) a row of CCS
 // positions in kSlots order (slot s of the node's generated code, then its d polynomial columns for a
@@ -696,7 +690,7 @@ int create(const Tables& T, const std::vector<double>& consts, int batch, Plan**
     }
     if (ctab.empty()) ctab.push_back(0);
     for (auto& x : dtab) if (x == 0xffffffffu) x = 0;   // padding of the shorter node kind
-    auto* p = new Plan();
+    auto p = std::make_unique<Plan>();   // freed, with all it owns, by every early return
     Args& a = p->a;
     for (int j = 0; j < NN; ++j) {
         for (int r = 0; r < NN; ++r) a.coll.C[j * NN + r] = T.coll.C[j][r];
@@ -723,33 +717,18 @@ int create(const Tables& T, const std::vector<double>& consts, int batch, Plan**
     a.ld8 = (unsigned)(8 * p->ld);
     const size_t rows_in = std::max((size_t)L.n_v, (size_t)L.n_p);
     if (rows_in * p->ld * 8 >= ((size_t)1 << 32)) {
-        destroy(p);
         why = "instance-minor inputs would exceed 4 GiB";
         return AWE_OK;
     }
-    auto up = [&](auto*& dst, const auto& v) -> int {
-        DGEN_TRY(hipMalloc((void**)&dst, sizeof(v[0]) * v.size()));
-        DGEN_TRY(hipMemcpy(dst, v.data(), sizeof(v[0]) * v.size(), hipMemcpyHostToDevice));
-        return AWE_OK;
-    };
-    int rc = up(p->d_dtab, dtab);
-    if (!rc) rc = up(p->d_ctab, ctab);
-    if (!rc) rc = up(p->d_coff, coff);
-    auto alloc = [&](double*& dst, size_t n) -> int {
-        DGEN_TRY(hipMalloc((void**)&dst, sizeof(double) * n));
-        return AWE_OK;
-    };
-    if (!rc) rc = alloc(p->d_VT, p->ld * L.n_v);
-    if (!rc) rc = alloc(p->d_PT, p->ld * L.n_p);
-    if (!rc) rc = alloc(p->d_objb, p->ld * (size_t)n_k * d * kObjRows);
-    if (!rc) rc = alloc(p->d_part, p->ld * (size_t)n_k * kNPart);
-    for (auto& e : p->ev)
-        if (!rc && hipEventCreate(&e) != hipSuccess) { err = "hipEventCreate"; rc = AWE_ERR_HIP; }
-    if (rc) {
-        destroy(p);
-        return rc;
-    }
-    *out = p;
+    DGEN_TRY(p->d_dtab.upload(dtab));
+    DGEN_TRY(p->d_ctab.upload(ctab));
+    DGEN_TRY(p->d_coff.upload(coff));
+    DGEN_TRY(p->d_VT.alloc(p->ld * L.n_v));
+    DGEN_TRY(p->d_PT.alloc(p->ld * L.n_p));
+    DGEN_TRY(p->d_objb.alloc(p->ld * (size_t)n_k * d * kObjRows));
+    DGEN_TRY(p->d_part.alloc(p->ld * (size_t)n_k * kNPart));
+    for (auto& e : p->ev) DGEN_TRY(e.create());
+    *out = p.release();
     return AWE_OK;
 }
 

@@ -17,12 +17,14 @@
 
 #include <cmath>
 #include <cstring>
+#include <memory>
 #include <type_traits>
 #include <string>
 #include <vector>
 
 #include "../../include/awegpu.h"
 #include "../../include/awempc.h"
+#include "host_util.hpp"
 #include "im_layout.hpp"
 #include "kite3_model.hpp"
 #include "kite3_nodejac.gen.hpp"
@@ -31,20 +33,7 @@
 namespace {
 
 using namespace k3t;
-
-thread_local std::string g_err;
-
-int fail(int code, const std::string& msg) {
-    g_err = msg;
-    return code;
-}
-
-#define MPC_TRY(expr)                                                                  \
-    do {                                                                               \
-        hipError_t _e = (expr);                                                        \
-        if (_e != hipSuccess)                                                          \
-            return fail(AWE_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-    } while (0)
+using namespace hostu;
 
 struct MArgs {
     int n_k, d, n_v, n_g, n_p, nnz, stride;
@@ -882,36 +871,34 @@ struct awempc_handle_s {
     Tables t;
     int batch = 0;
     std::vector<double> consts;
-    double* d_cst = nullptr;
-    awt::DevColl* d_coll = nullptr;
-    int* d_goff = nullptr;
-    int* d_gslot = nullptr;
-    uint32_t* d_gcode = nullptr;
-    double* d_fpart = nullptr;
-    double *d_V = nullptr, *d_P = nullptr, *d_f = nullptr, *d_g = nullptr, *d_grad = nullptr, *d_jac = nullptr;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    DevBuf<double> d_cst;
+    DevBuf<awt::DevColl> d_coll;
+    DevBuf<int> d_goff, d_gslot;
+    DevBuf<uint32_t> d_gcode;
+    DevBuf<double> d_fpart;
+    DevBuf<double> d_V, d_P, d_f, d_g, d_grad, d_jac;   // staging of the host entry points
+    Event ev[3];
     bool timed = false;
     // Hessian (built on first use: awempc_hess_init)
     HessTables ht;
     bool hess_ready = false;
     int hd_total = 0;
-    int *d_task = nullptr, *d_slot0 = nullptr, *d_nslot = nullptr, *d_ent_off = nullptr, *d_term_off = nullptr;
-    int *d_hgslot = nullptr, *d_xnslot = nullptr;
-    unsigned* d_terms = nullptr;
-    double* d_gpart = nullptr;
-    double *d_hsig = nullptr, *d_hlam = nullptr, *d_H = nullptr;
-    hipEvent_t hev[2] = {nullptr, nullptr};
+    DevBuf<int> d_task, d_slot0, d_nslot, d_ent_off, d_term_off, d_hgslot, d_xnslot;
+    DevBuf<unsigned> d_terms;
+    DevBuf<double> d_gpart;
+    DevBuf<double> d_hsig, d_hlam, d_H;
+    Event hev[2];
     bool htimed = false;
     // generated instance-minor path (awempc_eval_nlp_im)
     bool gen_ok = false;
     std::string gen_why;
     int gen_dstride = 0;
     size_t gen_ld = 0;                       // row length of VT / PT / fpart
-    unsigned *d_gdtab = nullptr, *d_gctab = nullptr;
-    int* d_gcoff = nullptr;
-    double *d_VT = nullptr, *d_PT = nullptr, *d_gfpart = nullptr;
+    DevBuf<unsigned> d_gdtab, d_gctab;
+    DevBuf<int> d_gcoff;
+    DevBuf<double> d_VT, d_PT, d_gfpart;
     double gen_kconst[8] = {};
-    hipEvent_t gev[4] = {nullptr, nullptr, nullptr, nullptr};
+    Event gev[4];
     bool gtimed = false;
 };
 
@@ -968,16 +955,13 @@ int build_gen(awempc_handle_s* h) {
     for (int r = 0; r < NN; ++r) h->gen_kconst[1 + r] = -h->t.coll.D[r];
     h->gen_dstride = dstride;
     h->gen_ld = (size_t)h->batch;
-    MPC_TRY(hipMalloc((void**)&h->d_gdtab, sizeof(unsigned) * dtab.size()));
-    MPC_TRY(hipMemcpy(h->d_gdtab, dtab.data(), sizeof(unsigned) * dtab.size(), hipMemcpyHostToDevice));
-    MPC_TRY(hipMalloc((void**)&h->d_gctab, sizeof(unsigned) * ctab.size()));
-    MPC_TRY(hipMemcpy(h->d_gctab, ctab.data(), sizeof(unsigned) * ctab.size(), hipMemcpyHostToDevice));
-    MPC_TRY(hipMalloc((void**)&h->d_gcoff, sizeof(int) * coff.size()));
-    MPC_TRY(hipMemcpy(h->d_gcoff, coff.data(), sizeof(int) * coff.size(), hipMemcpyHostToDevice));
-    MPC_TRY(hipMalloc((void**)&h->d_VT, sizeof(double) * h->gen_ld * T.lay.n_v));
-    MPC_TRY(hipMalloc((void**)&h->d_PT, sizeof(double) * h->gen_ld * T.lay.n_p));
-    MPC_TRY(hipMalloc((void**)&h->d_gfpart, sizeof(double) * h->gen_ld * n_k));
-    for (auto& e : h->gev) MPC_TRY(hipEventCreate(&e));
+    HIP_TRY(h->d_gdtab.upload(dtab));
+    HIP_TRY(h->d_gctab.upload(ctab));
+    HIP_TRY(h->d_gcoff.upload(coff));
+    HIP_TRY(h->d_VT.alloc(h->gen_ld * T.lay.n_v));
+    HIP_TRY(h->d_PT.alloc(h->gen_ld * T.lay.n_p));
+    HIP_TRY(h->d_gfpart.alloc(h->gen_ld * n_k));
+    for (auto& e : h->gev) HIP_TRY(e.create());
     h->gen_ok = true;
     return AWE_OK;
 }
@@ -993,9 +977,7 @@ int awempc_sparsity_jac_static(int n_k, int d, const double* consts, int n_const
     Tables T;
     std::string err;
     if (build_tables(n_k, d, consts, n_consts, T, err)) return fail(AWE_ERR_ARG, err);
-    *nnz = (int)T.row.size();
-    if (colind) std::memcpy(colind, T.colind.data(), sizeof(int) * T.colind.size());
-    if (row) std::memcpy(row, T.row.data(), sizeof(int) * T.row.size());
+    copy_ccs(nnz, colind, row, T.colind, T.row);
     return AWE_OK;
 }
 
@@ -1004,16 +986,11 @@ int awempc_create(int n_k, int d, const double* consts, int n_consts, int batch,
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(AWE_ERR_NODEVICE, "no HIP device");
     if (d < 2 || d > 5) return fail(AWE_ERR_ARG, "the MPC kernel is instantiated for 2 <= d <= 5");
-    auto* h = new awempc_handle_s();
+    auto h = std::make_unique<awempc_handle_s>();   // freed, with all it owns, by every early return
     std::string err;
-    if (build_tables(n_k, d, consts, n_consts, h->t, err)) {
-        delete h;
-        return fail(AWE_ERR_ARG, err);
-    }
-    if (consts[K3_C_N_K] != (double)n_k || consts[K3_C_D] != (double)d) {
-        delete h;
+    if (build_tables(n_k, d, consts, n_consts, h->t, err)) return fail(AWE_ERR_ARG, err);
+    if (consts[K3_C_N_K] != (double)n_k || consts[K3_C_D] != (double)d)
         return fail(AWE_ERR_ARG, "consts[K3_C_N_K], consts[K3_C_D] disagree with n_k, d");
-    }
     h->batch = batch;
     h->consts.assign(consts, consts + n_consts);
     awt::DevColl dc{};
@@ -1024,41 +1001,20 @@ int awempc_create(int n_k, int d, const double* consts, int n_consts, int batch,
     }
     for (int j = 0; j < d; ++j) dc.w[j] = h->t.coll.w[j];
     const Tables& T = h->t;
-#define MPC_UPLOAD(dst, src, n)                                                         \
-    MPC_TRY(hipMalloc((void**)&dst, sizeof(*dst) * (n)));                              \
-    MPC_TRY(hipMemcpy(dst, src, sizeof(*dst) * (n), hipMemcpyHostToDevice));
-    MPC_UPLOAD(h->d_cst, consts, n_consts);
-    MPC_UPLOAD(h->d_coll, &dc, 1);
-    MPC_UPLOAD(h->d_goff, T.goff.data(), T.goff.size());
-    MPC_UPLOAD(h->d_gslot, T.gslot.data(), T.gslot.size());
-    MPC_UPLOAD(h->d_gcode, T.gcode.data(), T.gcode.size());
-#undef MPC_UPLOAD
-    MPC_TRY(hipMalloc((void**)&h->d_fpart, sizeof(double) * (size_t)batch * n_k));
-    for (auto& e : h->ev) MPC_TRY(hipEventCreate(&e));
-    if (int rc = build_gen(h)) {
-        awempc_destroy(h);
-        return rc;
-    }
-    *out = h;
+    HIP_TRY(h->d_cst.upload(consts, n_consts));
+    HIP_TRY(h->d_coll.upload(&dc, 1));
+    HIP_TRY(h->d_goff.upload(T.goff));
+    HIP_TRY(h->d_gslot.upload(T.gslot));
+    HIP_TRY(h->d_gcode.upload(T.gcode));
+    HIP_TRY(h->d_fpart.alloc((size_t)batch * n_k));
+    for (auto& e : h->ev) HIP_TRY(e.create());
+    if (int rc = build_gen(h.get())) return rc;
+    *out = h.release();
     return AWE_OK;
 }
 
 int awempc_destroy(awempc_handle h) {
-    if (!h) return AWE_OK;
-    void* bufs[] = {h->d_cst, h->d_coll, h->d_goff, h->d_gslot, h->d_gcode, h->d_fpart,
-                    h->d_V, h->d_P, h->d_f, h->d_g, h->d_grad, h->d_jac,
-                    h->d_task, h->d_slot0, h->d_nslot, h->d_ent_off, h->d_term_off, h->d_hgslot, h->d_xnslot,
-                    h->d_terms, h->d_gpart, h->d_hsig, h->d_hlam, h->d_H,
-                    h->d_gdtab, h->d_gctab, h->d_gcoff, h->d_VT, h->d_PT, h->d_gfpart};
-    for (void* p : bufs)
-        if (p) (void)hipFree(p);
-    for (auto& e : h->ev)
-        if (e) (void)hipEventDestroy(e);
-    for (auto& e : h->hev)
-        if (e) (void)hipEventDestroy(e);
-    for (auto& e : h->gev)
-        if (e) (void)hipEventDestroy(e);
-    delete h;
+    delete h;   // the members free their device memory and events
     return AWE_OK;
 }
 
@@ -1073,8 +1029,7 @@ int awempc_sizes(awempc_handle h, int* n_v, int* n_g, int* n_p, int* nnz) {
 
 int awempc_sparsity_jac(awempc_handle h, int* colind, int* row) {
     if (!h || !colind || !row) return fail(AWE_ERR_ARG, "null argument");
-    std::memcpy(colind, h->t.colind.data(), sizeof(int) * h->t.colind.size());
-    std::memcpy(row, h->t.row.data(), sizeof(int) * h->t.row.size());
+    copy_ccs(nullptr, colind, row, h->t.colind, h->t.row);
     return AWE_OK;
 }
 
@@ -1086,7 +1041,7 @@ int awempc_eval_nlp(awempc_handle h, const double* V, const double* p, double* f
     MArgs a{T.lay.n_k, T.lay.d, T.lay.n_v, T.lay.n_g, T.lay.n_p, (int)T.row.size(), T.lay.stride,
             V, p, f, g, grad_f, jac, h->d_cst, h->d_coll, h->d_goff, h->d_gslot, h->d_gcode, h->d_fpart};
     const dim3 grid((unsigned)(h->batch * T.lay.n_k));
-    MPC_TRY(hipEventRecord(h->ev[0], s));
+    HIP_TRY(hipEventRecord(h->ev[0], s));
     switch (T.lay.d) {
         case 2: mpc_interval_kernel<2><<<grid, 64 * waves_for<2>(), 0, s>>>(a); break;
         case 3: mpc_interval_kernel<3><<<grid, 64 * waves_for<3>(), 0, s>>>(a); break;
@@ -1094,11 +1049,11 @@ int awempc_eval_nlp(awempc_handle h, const double* V, const double* p, double* f
         case 5: mpc_interval_kernel<5><<<grid, 64 * waves_for<5>(), 0, s>>>(a); break;
         default: return fail(AWE_ERR_ARG, "unsupported d");
     }
-    MPC_TRY(hipGetLastError());
-    MPC_TRY(hipEventRecord(h->ev[1], s));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(h->ev[1], s));
     mpc_finalize_kernel<<<dim3((unsigned)h->batch), 64, 0, s>>>(a);
-    MPC_TRY(hipGetLastError());
-    MPC_TRY(hipEventRecord(h->ev[2], s));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(h->ev[2], s));
     h->timed = true;
     return AWE_OK;
 }
@@ -1142,11 +1097,11 @@ int awempc_eval_nlp_im(awempc_handle h, const double* V, const double* p, double
     a.ld8 = (unsigned)(8 * h->gen_ld);
     a.ldj8 = (unsigned)(8 * ld);
     for (int i = 0; i < 8; ++i) a.kconst[i] = h->gen_kconst[i];
-    MPC_TRY(hipEventRecord(h->gev[0], s));
+    HIP_TRY(hipEventRecord(h->gev[0], s));
     const dim3 tgrid((unsigned)((T.lay.n_v + T.lay.n_p + 63) / 64), (unsigned)a.nib);
     im::transpose_in_kernel<<<tgrid, 256, 0, s>>>(V, p, h->d_VT, h->d_PT, B, T.lay.n_v, T.lay.n_p, (int)h->gen_ld);
-    MPC_TRY(hipGetLastError());
-    MPC_TRY(hipEventRecord(h->gev[1], s));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(h->gev[1], s));
     const int n_tiles = a.nib * (a.n_k + (a.n_k + kGenShootWaves - 1) / kGenShootWaves) * kGenStripGroups +
                         (AWE_MPC_EXTRA_TILES ? a.nib * ((a.n_k + kGenShootWaves - 1) / kGenShootWaves) : 0);
     const dim3 ngrid((unsigned)im::xcd_grid(n_tiles));
@@ -1161,29 +1116,29 @@ int awempc_eval_nlp_im(awempc_handle h, const double* V, const double* p, double
         default: return fail(AWE_ERR_ARG, "unsupported d");
     }
 #undef MPC_GEN_NODE
-    MPC_TRY(hipGetLastError());
-    MPC_TRY(hipEventRecord(h->gev[2], s));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(h->gev[2], s));
     mpc_gen_finalize_kernel<<<dim3((unsigned)a.nib), 64, 0, s>>>(h->d_VT, h->d_PT, h->d_gfpart, f, grad_f, a);
-    MPC_TRY(hipGetLastError());
-    MPC_TRY(hipEventRecord(h->gev[3], s));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(h->gev[3], s));
     h->gtimed = true;
     return AWE_OK;
 }
 
 int awempc_last_kernel_ms_im(awempc_handle h, float* ms_in, float* ms_node, float* ms_fin) {
     if (!h || !h->gtimed) return fail(AWE_ERR_ARG, "no timed instance-minor evaluation yet");
-    MPC_TRY(hipEventSynchronize(h->gev[3]));
-    if (ms_in) MPC_TRY(hipEventElapsedTime(ms_in, h->gev[0], h->gev[1]));
-    if (ms_node) MPC_TRY(hipEventElapsedTime(ms_node, h->gev[1], h->gev[2]));
-    if (ms_fin) MPC_TRY(hipEventElapsedTime(ms_fin, h->gev[2], h->gev[3]));
+    HIP_TRY(hipEventSynchronize(h->gev[3]));
+    if (ms_in) HIP_TRY(hipEventElapsedTime(ms_in, h->gev[0], h->gev[1]));
+    if (ms_node) HIP_TRY(hipEventElapsedTime(ms_node, h->gev[1], h->gev[2]));
+    if (ms_fin) HIP_TRY(hipEventElapsedTime(ms_fin, h->gev[2], h->gev[3]));
     return AWE_OK;
 }
 
 int awempc_last_kernel_ms(awempc_handle h, float* ms_main, float* ms_fin) {
     if (!h || !h->timed) return fail(AWE_ERR_ARG, "no timed evaluation yet");
-    MPC_TRY(hipEventSynchronize(h->ev[2]));
-    if (ms_main) MPC_TRY(hipEventElapsedTime(ms_main, h->ev[0], h->ev[1]));
-    if (ms_fin) MPC_TRY(hipEventElapsedTime(ms_fin, h->ev[1], h->ev[2]));
+    HIP_TRY(hipEventSynchronize(h->ev[2]));
+    if (ms_main) HIP_TRY(hipEventElapsedTime(ms_main, h->ev[0], h->ev[1]));
+    if (ms_fin) HIP_TRY(hipEventElapsedTime(ms_fin, h->ev[1], h->ev[2]));
     return AWE_OK;
 }
 
@@ -1192,31 +1147,11 @@ int awempc_eval_nlp_host(awempc_handle h, const double* V, const double* p, doub
     if (!h || !V || !p || !f || !g || !grad_f || !jac) return fail(AWE_ERR_ARG, "null argument");
     const Tables& T = h->t;
     const size_t nb = (size_t)h->batch, nnz = T.row.size();
-    if (!h->d_V) {
-        MPC_TRY(hipMalloc((void**)&h->d_V, sizeof(double) * nb * T.lay.n_v));
-        MPC_TRY(hipMalloc((void**)&h->d_P, sizeof(double) * nb * T.lay.n_p));
-        MPC_TRY(hipMalloc((void**)&h->d_f, sizeof(double) * nb));
-        MPC_TRY(hipMalloc((void**)&h->d_g, sizeof(double) * nb * T.lay.n_g));
-        MPC_TRY(hipMalloc((void**)&h->d_grad, sizeof(double) * nb * T.lay.n_v));
-        MPC_TRY(hipMalloc((void**)&h->d_jac, sizeof(double) * nb * nnz));
-    }
-    MPC_TRY(hipMemcpy(h->d_V, V, sizeof(double) * nb * T.lay.n_v, hipMemcpyHostToDevice));
-    MPC_TRY(hipMemcpy(h->d_P, p, sizeof(double) * nb * T.lay.n_p, hipMemcpyHostToDevice));
-    int rc = awempc_eval_nlp(h, h->d_V, h->d_P, h->d_f, h->d_g, h->d_grad, h->d_jac, nullptr);
-    if (rc) return rc;
-    MPC_TRY(hipDeviceSynchronize());
-    MPC_TRY(hipMemcpy(f, h->d_f, sizeof(double) * nb, hipMemcpyDeviceToHost));
-    MPC_TRY(hipMemcpy(g, h->d_g, sizeof(double) * nb * T.lay.n_g, hipMemcpyDeviceToHost));
-    MPC_TRY(hipMemcpy(grad_f, h->d_grad, sizeof(double) * nb * T.lay.n_v, hipMemcpyDeviceToHost));
-    MPC_TRY(hipMemcpy(jac, h->d_jac, sizeof(double) * nb * nnz, hipMemcpyDeviceToHost));
-    auto finite = [](const double* x, size_t n) {
-        for (size_t i = 0; i < n; ++i)
-            if (!std::isfinite(x[i])) return false;
-        return true;
-    };
-    if (!finite(f, nb) || !finite(g, nb * T.lay.n_g) || !finite(grad_f, nb * T.lay.n_v) || !finite(jac, nb * nnz))
-        return fail(AWE_ERR_NONFINITE, "non-finite output");
-    return AWE_OK;
+    return host_round_trip(
+        {{h->d_V, V, nb * T.lay.n_v}, {h->d_P, p, nb * T.lay.n_p}},
+        {{h->d_f, f, nb}, {h->d_g, g, nb * T.lay.n_g}, {h->d_grad, grad_f, nb * T.lay.n_v}, {h->d_jac, jac, nb * nnz}},
+        [&] { return awempc_eval_nlp(h, h->d_V, h->d_P, h->d_f, h->d_g, h->d_grad, h->d_jac, nullptr); },
+        "non-finite output");
 }
 
 // ---- nlp_hess_l ------------------------------------------------------------------------------
@@ -1227,9 +1162,7 @@ int awempc_sparsity_hess_static(int n_k, int d, const double* consts, int n_cons
     std::string err;
     if (build_tables(n_k, d, consts, n_consts, T, err) || build_hess_tables(T, consts, H, err))
         return fail(AWE_ERR_ARG, err);
-    *nnz = H.nnz;
-    if (colind) std::memcpy(colind, H.colind.data(), sizeof(int) * H.colind.size());
-    if (row) std::memcpy(row, H.row.data(), sizeof(int) * H.row.size());
+    copy_ccs(nnz, colind, row, H.colind, H.row);
     return AWE_OK;
 }
 
@@ -1242,20 +1175,16 @@ int awempc_hess_init(awempc_handle h, int* nnz) {
         h->hd_total = H.ntask[0] + h->t.lay.d * H.ntask[1];
         if ((size_t)h->hd_total * sizeof(double) > 60 * 1024) return fail(AWE_ERR_ARG, "Hessian tasks exceed the LDS budget");
         if ((int)H.gslot.size() > 64) return fail(AWE_ERR_ARG, "too many global Hessian entries");
-#define MPC_UPLOAD(dst, vec)                                                               \
-        MPC_TRY(hipMalloc((void**)&dst, sizeof(*dst) * (vec).size()));                      \
-        MPC_TRY(hipMemcpy(dst, (vec).data(), sizeof(*dst) * (vec).size(), hipMemcpyHostToDevice));
-        MPC_UPLOAD(h->d_task, H.task);
-        MPC_UPLOAD(h->d_slot0, H.slot0);
-        MPC_UPLOAD(h->d_nslot, H.nslot);
-        MPC_UPLOAD(h->d_ent_off, H.ent_off);
-        MPC_UPLOAD(h->d_term_off, H.term_off);
-        MPC_UPLOAD(h->d_terms, H.terms);
-        MPC_UPLOAD(h->d_hgslot, H.gslot);
-        MPC_UPLOAD(h->d_xnslot, H.xnslot);
-#undef MPC_UPLOAD
-        MPC_TRY(hipMalloc((void**)&h->d_gpart, sizeof(double) * (size_t)h->batch * h->t.lay.n_k * std::max<size_t>(1, H.gslot.size())));
-        for (auto& e : h->hev) MPC_TRY(hipEventCreate(&e));
+        HIP_TRY(h->d_task.upload(H.task));
+        HIP_TRY(h->d_slot0.upload(H.slot0));
+        HIP_TRY(h->d_nslot.upload(H.nslot));
+        HIP_TRY(h->d_ent_off.upload(H.ent_off));
+        HIP_TRY(h->d_term_off.upload(H.term_off));
+        HIP_TRY(h->d_terms.upload(H.terms));
+        HIP_TRY(h->d_hgslot.upload(H.gslot));
+        HIP_TRY(h->d_xnslot.upload(H.xnslot));
+        HIP_TRY(h->d_gpart.alloc((size_t)h->batch * h->t.lay.n_k * std::max<size_t>(1, H.gslot.size())));
+        for (auto& e : h->hev) HIP_TRY(e.create());
         h->hess_ready = true;
     }
     if (nnz) *nnz = h->ht.nnz;
@@ -1266,8 +1195,7 @@ int awempc_sparsity_hess(awempc_handle h, int* colind, int* row) {
     if (!h || !colind || !row) return fail(AWE_ERR_ARG, "null argument");
     int rc = awempc_hess_init(h, nullptr);
     if (rc) return rc;
-    std::memcpy(colind, h->ht.colind.data(), sizeof(int) * h->ht.colind.size());
-    std::memcpy(row, h->ht.row.data(), sizeof(int) * h->ht.row.size());
+    copy_ccs(nullptr, colind, row, h->ht.colind, h->ht.row);
     return AWE_OK;
 }
 
@@ -1286,7 +1214,7 @@ int awempc_eval_hess(awempc_handle h, const double* V, const double* p, const do
              h->d_hgslot, h->d_xnslot};
     const dim3 grid((unsigned)(h->batch * T.lay.n_k));
     const size_t lds = sizeof(double) * (size_t)h->hd_total;
-    MPC_TRY(hipEventRecord(h->hev[0], s));
+    HIP_TRY(hipEventRecord(h->hev[0], s));
     switch (T.lay.d) {
         case 2: mpc_hess_kernel<2><<<grid, kHessThreads, lds, s>>>(ha); break;
         case 3: mpc_hess_kernel<3><<<grid, kHessThreads, lds, s>>>(ha); break;
@@ -1294,18 +1222,18 @@ int awempc_eval_hess(awempc_handle h, const double* V, const double* p, const do
         case 5: mpc_hess_kernel<5><<<grid, kHessThreads, lds, s>>>(ha); break;
         default: return fail(AWE_ERR_ARG, "unsupported d");
     }
-    MPC_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     mpc_hess_finalize_kernel<<<dim3((unsigned)h->batch), 64, 0, s>>>(ha);
-    MPC_TRY(hipGetLastError());
-    MPC_TRY(hipEventRecord(h->hev[1], s));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(h->hev[1], s));
     h->htimed = true;
     return AWE_OK;
 }
 
 int awempc_last_hess_ms(awempc_handle h, float* ms) {
     if (!h || !h->htimed) return fail(AWE_ERR_ARG, "no timed Hessian evaluation yet");
-    MPC_TRY(hipEventSynchronize(h->hev[1]));
-    if (ms) MPC_TRY(hipEventElapsedTime(ms, h->hev[0], h->hev[1]));
+    HIP_TRY(hipEventSynchronize(h->hev[1]));
+    if (ms) HIP_TRY(hipEventElapsedTime(ms, h->hev[0], h->hev[1]));
     return AWE_OK;
 }
 
@@ -1316,26 +1244,12 @@ int awempc_eval_hess_host(awempc_handle h, const double* V, const double* p, con
     if (rc) return rc;
     const Tables& T = h->t;
     const size_t nb = (size_t)h->batch, hnnz = h->ht.nnz;
-    if (!h->d_V) {
-        MPC_TRY(hipMalloc((void**)&h->d_V, sizeof(double) * nb * T.lay.n_v));
-        MPC_TRY(hipMalloc((void**)&h->d_P, sizeof(double) * nb * T.lay.n_p));
-    }
-    if (!h->d_H) {
-        MPC_TRY(hipMalloc((void**)&h->d_hsig, sizeof(double) * nb));
-        MPC_TRY(hipMalloc((void**)&h->d_hlam, sizeof(double) * nb * T.lay.n_g));
-        MPC_TRY(hipMalloc((void**)&h->d_H, sizeof(double) * nb * hnnz));
-    }
-    MPC_TRY(hipMemcpy(h->d_V, V, sizeof(double) * nb * T.lay.n_v, hipMemcpyHostToDevice));
-    MPC_TRY(hipMemcpy(h->d_P, p, sizeof(double) * nb * T.lay.n_p, hipMemcpyHostToDevice));
-    MPC_TRY(hipMemcpy(h->d_hsig, sigma, sizeof(double) * nb, hipMemcpyHostToDevice));
-    MPC_TRY(hipMemcpy(h->d_hlam, lam_g, sizeof(double) * nb * T.lay.n_g, hipMemcpyHostToDevice));
-    rc = awempc_eval_hess(h, h->d_V, h->d_P, h->d_hsig, h->d_hlam, h->d_H, nullptr);
-    if (rc) return rc;
-    MPC_TRY(hipDeviceSynchronize());
-    MPC_TRY(hipMemcpy(H, h->d_H, sizeof(double) * nb * hnnz, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < nb * hnnz; ++i)
-        if (!std::isfinite(H[i])) return fail(AWE_ERR_NONFINITE, "non-finite Hessian");
-    return AWE_OK;
+    return host_round_trip(
+        {{h->d_V, V, nb * T.lay.n_v}, {h->d_P, p, nb * T.lay.n_p}, {h->d_hsig, sigma, nb},
+         {h->d_hlam, lam_g, nb * T.lay.n_g}},
+        {{h->d_H, H, nb * hnnz}},
+        [&] { return awempc_eval_hess(h, h->d_V, h->d_P, h->d_hsig, h->d_hlam, h->d_H, nullptr); },
+        "non-finite Hessian");
 }
 
 }  // extern "C"

@@ -123,6 +123,12 @@ class FdHessian:
     def __getattr__(self, name):
         return getattr(self.ev, name)
 
+    hess_instance_minor = False      # H per instance, in this class's own (denser) pattern
+
+    def alloc_hess(self, device="cuda", instance_minor=False):
+        import torch
+        return torch.zeros(self.ev.batch, self.nnz_h, dtype=torch.float64, device=device)
+
     def sparsity_hess(self):
         return self.hcolind.copy(), self.hrow.copy()
 

@@ -43,6 +43,7 @@ import torch
 
 from . import det
 from .ipm_measures import Measures
+from .nlp_binding import solver_tensors
 from . import problem as pb
 
 
@@ -185,14 +186,11 @@ class DeviceNlp:
         self.V = torch.tensor(np.tile(self.x_fix, (B, 1)), device=device)
         self.f = torch.zeros(B, **f64)
         self.g = torch.zeros(B, n_g, **f64)
-        self.grad = ev.alloc_grad(device) if hasattr(ev, "alloc_grad") else torch.zeros(B, n_v, **f64)
-        # J_g in the evaluator's instance-minor layout where it has one (the AP2 evaluator writes it
-        # with coalesced stores, awe_eval_nlp_im); a [B, nnz] view either way
-        self.jac = ev.alloc_jac(device) if hasattr(ev, "alloc_jac") else torch.zeros(B, ev.nnz, **f64)
+        # grad f and J_g in the evaluator's own layout: instance-minor where it has one (the AP2
+        # evaluator writes it with coalesced stores, awe_eval_nlp_im); [B, n] views either way
         # H instance-minor where the evaluator's Hessian kernel writes it that way (the generated
         # Hessian, awe_eval_hess_im); per instance for the hyper-dual kernels
-        self.h_im = getattr(ev, "hess_path", None) == "generated" and hasattr(ev, "alloc_hess")
-        self.H = ev.alloc_hess(device) if self.h_im else torch.zeros(B, ev.nnz_h, **f64)
+        self.grad, self.jac, self.H, self.h_im = solver_tensors(ev, B, n_v, device)
         self.sig = torch.ones(B, **f64)
         self.free_t = torch.tensor(self.free, device=device)
         self.ineq_t = torch.tensor(self.ineq, device=device)

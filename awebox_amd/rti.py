@@ -36,6 +36,7 @@ import torch
 from . import kite3 as k3
 from .collocation import coefficients
 from .ipm import scatter_sum
+from .nlp_binding import solver_tensors
 
 
 def orbit_states(orbit: k3.CircularOrbit, t: np.ndarray) -> np.ndarray:
@@ -205,8 +206,7 @@ class BatchedRti:
         self.f = torch.zeros(B, **f64)
         self.g = torch.zeros(B, n_g, **f64)
         # the evaluator's preferred layout (instance-minor for the HIP MPC evaluator's generated path)
-        self.grad = self.ev.alloc_grad(self.dev) if hasattr(self.ev, "alloc_grad") else torch.zeros(B, n_v, **f64)
-        self.jac = self.ev.alloc_jac(self.dev) if hasattr(self.ev, "alloc_jac") else torch.zeros(B, self.ev.nnz, **f64)
+        self.grad, self.jac, _, _ = solver_tensors(self.ev, B, n_v, self.dev, hess=False)
         self.free_t, self.eq_t = t(self.free), t(self.eq)
         self.path_t = t(path)
         self.u0_idx = t(lay.u(0))

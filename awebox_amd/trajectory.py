@@ -54,19 +54,15 @@ class _pinned_path:
     def __enter__(self):
         ev = self.ev
         self.saved = None
-        if self.eval_path is not None and hasattr(ev, "path"):
-            self.saved = (ev.path, getattr(ev, "hess_mode", None))
+        if self.eval_path is not None and getattr(ev, "has_eval_paths", False):
+            self.saved = (ev.path, ev.hess_mode)
             ev.path = self.eval_path
-            if hasattr(ev, "hess_path"):
-                ev.hess_path = "follow"
+            ev.hess_path = "follow"
         return ev
 
     def __exit__(self, *exc):
         if self.saved is not None:
-            path, hmode = self.saved
-            self.ev.path = path
-            if hmode is not None:
-                self.ev.hess_path = hmode
+            self.ev.path, self.ev.hess_path = self.saved
         return False
 
 

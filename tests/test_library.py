@@ -106,5 +106,33 @@ def test_model_libraries_export_every_header_symbol(lib_attr, header, prefix, mo
     lib = mod.load_library()
     for name in declared:
         assert getattr(lib, name) is not None
-    if hasattr(mod, "EXPORTED_SYMBOLS"):
-        assert declared == set(mod.EXPORTED_SYMBOLS)
+    assert declared == set(mod.EXPORTED_SYMBOLS)
+
+
+def _prototype_arity(header_text, prefix):
+    """{function: number of parameters} of every prototype of the header (``void`` is none)."""
+    protos = re.findall(r"^(?:int|const char\*)\s+(" + prefix + r"\w+)\(([^)]*)\)\s*;", header_text, re.M)
+    return {name: 0 if params.strip() in ("", "void") else params.count(",") + 1 for name, params in protos}
+
+
+@pytest.mark.parametrize("lib_attr,header,prefix,module", [
+    ("LIB", "awegpu.h", "awe_", "awebox_amd.evaluator"),
+    ("LIB_DUAL", "awedual.h", "adl_", "awebox_amd.dual_evaluator"),
+    ("LIB_MPC", "awempc.h", "awempc_", "awebox_amd.mpc")])
+def test_bindings_declare_every_header_prototype(lib_attr, header, prefix, module):
+    """Every function a model header declares is bound by the ctypes signature table with as many
+    argtypes as the prototype has parameters: a wrong table row fails here, without a GPU."""
+    import importlib
+
+    from awebox_amd import build as B
+    B.build_one(getattr(B, lib_attr))
+    text = open(os.path.join(os.path.dirname(HEADER), header)).read()
+    arity = _prototype_arity(text, prefix)
+    assert set(arity) == set(re.findall(r"^(?:int|const char\*)\s+(" + prefix + r"\w+)\(", text, re.M))
+    mod = importlib.import_module(module)
+    lib = mod.load_library()
+    assert set(arity) == set(mod.EXPORTED_SYMBOLS)
+    for name, n in sorted(arity.items()):
+        fn = getattr(lib, name)
+        assert fn.argtypes is not None, f"{name} has no declared argtypes"
+        assert len(fn.argtypes) == n, f"{name}: {len(fn.argtypes)} argtypes bound, {n} parameters declared"
