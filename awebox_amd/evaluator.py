@@ -179,8 +179,10 @@ class Ap2Evaluator(nb.NlpEvaluator):
 
     # ---------------------------------------------- timers -----------------------------
     def last_kernel_ms_soa(self):
-        """HIP-event times of the last instance-minor call: input transpose, node kernel, interval
-        kernel, finalize, output transpose (ms)."""
+        """HIP-event times of the last instance-minor call (ms): input transpose; the Radau kernel
+        (node code and its workgroups' interval pass) with the shooting kernel beside it on a second
+        stream; the wait for that stream's join after the Radau kernel (there is no separate interval
+        kernel); finalize; output transpose."""
         ms = (ctypes.c_float * 5)()
         self._call("last_kernel_ms_soa", ms)
         return [float(x) for x in ms]

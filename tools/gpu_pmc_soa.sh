@@ -1,6 +1,6 @@
 #!/bin/bash
-# PMC passes over the instance-minor evaluation path (ap2_soa_in / shoot / radau, the interval
-# kernel, B=2048, tools/pmc_kernels.py --ap2): HBM bytes (FETCH_SIZE, WRITE_SIZE), instruction mix,
+# PMC passes over the instance-minor evaluation path (ap2_soa_shoot / radau, finalize,
+# B=2048, tools/pmc_kernels.py --ap2): HBM bytes (FETCH_SIZE, WRITE_SIZE), instruction mix,
 # wave-state cycles, one counter group per run with the kernel trace only; then the kernel-trace
 # statistics of the same program.
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
