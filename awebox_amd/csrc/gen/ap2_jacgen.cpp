@@ -55,6 +55,47 @@ struct KindOut {
 
 std::vector<int> ko_dbp_dirs;   // directions of the Radau node's dbp entries, in order
 
+// Moves every sin / cos of a leaf (th[i], in(i), cst[i]) and the leaf's load to the top of an emitted body.
+// On the device sin and cos are the only operations of the node code that expand to a branch (the
+// large-argument reduction of the library's implementation), so one of them in the middle of the body
+// cuts the straight-line code into two basic blocks.  The shooting node has one, cos(th[22]) of a path
+// constraint, which the pressure schedule put 59 % into the body: 311 doubles were live across its
+// branch, where the emitted order has 123, and the register allocator sent 147 of them to scratch (the
+// Radau node has none and compiles to one block without scratch).  At the top nothing is live yet, the
+// branch costs nothing, and the result stays in a register (one more live double) until its first use.
+// The operations and their operands are unchanged; only the position of these statements is.
+std::string hoist_leaf_trig(const std::string& body) {
+    std::vector<std::string> lines;
+    for (size_t p = 0; p < body.size();) {
+        const size_t e = body.find('\n', p);
+        lines.push_back(body.substr(p, e - p));
+        p = e + 1;
+    }
+    const std::string def = "    const double ";
+    auto name_of = [&](const std::string& l) { return l.substr(def.size(), l.find(' ', def.size()) - def.size()); };
+    auto rhs_of = [&](const std::string& l) { return l.substr(l.find(" = ") + 3); };
+    std::vector<char> moved(lines.size(), 0);
+    for (size_t i = 0; i < lines.size(); ++i) {
+        if (lines[i].compare(0, def.size(), def) != 0) continue;
+        const std::string rhs = rhs_of(lines[i]);
+        if (rhs.compare(0, 6, "::sin(") != 0 && rhs.compare(0, 6, "::cos(") != 0) continue;
+        const std::string arg = rhs.substr(6, rhs.find(')') - 6);
+        for (size_t j = 0; j < i; ++j) {
+            if (lines[j].compare(0, def.size(), def) != 0 || name_of(lines[j]) != arg) continue;
+            const std::string r = rhs_of(lines[j]);
+            if (r.compare(0, 3, "th[") == 0 || r.compare(0, 3, "in(") == 0 || r.compare(0, 4, "cst[") == 0)
+                moved[j] = moved[i] = 1;
+            break;
+        }
+        if (!moved[i]) std::fprintf(stderr, "note: %s stays in place (its argument is not a leaf)\n", rhs.c_str());
+    }
+    std::string out;
+    for (int pass = 1; pass >= 0; --pass)
+        for (size_t i = 0; i < lines.size(); ++i)
+            if (moved[i] == pass) out += lines[i] + "\n";
+    return out;
+}
+
 KindOut generate(int kind, const std::vector<double>& cst, const awt::ColorTabs& ct, int n_strips) {
     awe::Tape tape;
     awe::active_tape() = &tape;
@@ -156,6 +197,7 @@ KindOut generate(int kind, const std::vector<double>& cst, const awt::ColorTabs&
         awe::EmitStats st;
         const int before = slot_base;
         std::string body = awe::emit(tape, part, st, true, fence, sidx > 0, slot_base);
+        if (kind == 0) body = hoist_leaf_trig(body);   // the Radau node has no sin / cos
         slot_base = before + st.n_tan;
         ko.body += "    {   // strip " + std::to_string(sidx) + "\n" + body + "    }\n";
         ko.st.ops += st.ops; ko.st.flops += st.flops; ko.st.transcendental += st.transcendental;
