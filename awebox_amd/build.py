@@ -51,16 +51,17 @@ GENERATORS = [(GEN_HEADER, "ap2_jacgen.cpp", GEN_SOURCES, "ap2"), (HESS_HEADER, 
 # content hash of GEN_SOURCES recorded in the generated header's first line: the header is stale
 # when the hash differs (file times do not survive a checkout or the copy to the GPU box)
 _HASH_TAG = "// inputs-sha1: "
-_COMMON = [os.path.join(CSRC, f) for f in ("ap2_model.hpp", "ap2_tables.hpp", "scalar.hpp", "host_util.hpp")] + [
+_COMMON = [os.path.join(CSRC, f) for f in ("ap2_model.hpp", "ap2_tables.hpp", "scalar.hpp", "host_util.hpp",
+                                           "im_layout.hpp", "im_tables.hpp")] + [
     os.path.join(INCLUDE, "awegpu.h")]
 TARGETS = {
     LIB: ([os.path.join(CSRC, "awegpu.hip")], _COMMON + [GEN_HEADER, HESS_HEADER]),
     LIB_MPC: ([os.path.join(CSRC, "awempc.hip")],
-              _COMMON + [os.path.join(CSRC, f) for f in ("kite3_model.hpp", "kite3_tables.hpp", "im_layout.hpp")]
+              _COMMON + [os.path.join(CSRC, f) for f in ("kite3_model.hpp", "kite3_tables.hpp")]
               + [os.path.join(INCLUDE, "awempc.h"), K3_HEADER]),
     LIB_DUAL: ([os.path.join(CSRC, "awedual.hip"), os.path.join(CSRC, "awedual_gen.hip")],
                _COMMON + [os.path.join(CSRC, f) for f in ("dual_model.hpp", "dual_tables.hpp", "dual_hess_tables.hpp",
-                                                          "awedual_gen.hpp", "im_layout.hpp")]
+                                                          "awedual_gen.hpp")]
                + [os.path.join(INCLUDE, "awedual.h"), DUAL_HEADER]),
     LIB_LU: ([os.path.join(CSRC, "batched_lu.hip")], [os.path.join(INCLUDE, "awelu.h")]),
 }

@@ -929,19 +929,7 @@ __global__ __launch_bounds__(64) void dual_hess_finalize_kernel(HDArgs ha) {
     }
 }
 
-template <int D>
-int launch_hess(const HDArgs& ha, int batch, size_t dyn, hipStream_t s) {
-    // the LDS image (tangents + direction-pair Hessian) exceeds 64 KiB: raise the dynamic limit
-    HIP_TRY(hipFuncSetAttribute((const void*)dual_hess_kernel<D>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
-    dual_hess_kernel<D><<<dim3((unsigned)(batch * ha.a.n_k)), kBlock, dyn, s>>>(ha);
-    return 0;
-}
-
-template <int D>
-int launch(const DArgs& a, int batch, size_t dyn, hipStream_t s) {
-    dual_interval_kernel<D><<<dim3((unsigned)(batch * a.n_k)), kBlock, dyn, s>>>(a);
-    return 0;
-}
+int unsupported_d() { return fail(AWE_ERR_ARG, "unsupported d"); }
 
 }  // namespace
 
@@ -996,12 +984,8 @@ static DArgs make_args(adl_handle h, const double* V, const double* P) {
 }
 
 static size_t hess_dyn_fixed(int d) {
-    switch (d) {
-        case 2: return hess_dyn_fixed_doubles<2>();
-        case 3: return hess_dyn_fixed_doubles<3>();
-        case 4: return hess_dyn_fixed_doubles<4>();
-        default: return hess_dyn_fixed_doubles<5>();
-    }
+    return for_degree<2>(d, [](auto dc) { return (size_t)hess_dyn_fixed_doubles<decltype(dc)::value>(); },
+                         [] { return (size_t)0; });   // adl_create admits 2 <= d <= 5
 }
 
 // builds and uploads the Hessian tables on first use
@@ -1044,16 +1028,15 @@ static int launch_hess_all(adl_handle h, const double* V, const double* P, const
     ha.slot0 = h->d_slot0; ha.nslot = h->d_nslot; ha.gslot = h->d_hgslot; ha.gcol = h->d_gcol; ha.grow = h->d_grow;
     ha.sigma = sigma; ha.lam = lam; ha.H = Hv; ha.gpart = h->d_gpart; ha.apart = h->d_apart;
     ha.hnnz = H.nnz; ha.ng = (int)H.gslot.size(); ha.hd_total = h->hd_total;
-    int rc = 0;
     HIP_TRY(hipEventRecord(h->hev[0], s));
-    switch (h->t.lay.d) {
-        case 2: rc = launch_hess<2>(ha, h->batch, h->hess_dyn, s); break;
-        case 3: rc = launch_hess<3>(ha, h->batch, h->hess_dyn, s); break;
-        case 4: rc = launch_hess<4>(ha, h->batch, h->hess_dyn, s); break;
-        case 5: rc = launch_hess<5>(ha, h->batch, h->hess_dyn, s); break;
-        default: return fail(AWE_ERR_ARG, "unsupported d");
-    }
-    if (rc) return rc;
+    if (int rc = for_degree<2>(h->t.lay.d, [&](auto dc) -> int {
+            constexpr int D = decltype(dc)::value;
+            // the LDS image (tangents + direction-pair Hessian) exceeds 64 KiB: raise the dynamic limit
+            HIP_TRY(hipFuncSetAttribute((const void*)dual_hess_kernel<D>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        (int)h->hess_dyn));
+            dual_hess_kernel<D><<<dim3((unsigned)(h->batch * ha.a.n_k)), kBlock, h->hess_dyn, s>>>(ha);
+            return AWE_OK;
+        }, unsupported_d)) return rc;
     HIP_TRY(hipGetLastError());
     dual_hess_finalize_kernel<<<dim3((unsigned)h->batch), 64, 0, s>>>(ha);
     HIP_TRY(hipGetLastError());
@@ -1208,13 +1191,10 @@ int adl_eval_nlp(adl_handle h, const double* V, const double* P, double* f, doub
     a.f = f; a.g = g; a.grad = grad_f; a.jac = jac;
     const size_t dyn = sizeof(double) * (size_t)T.tang_total;
     HIP_TRY(hipEventRecord(h->ev[0], s));
-    switch (L.d) {
-        case 2: launch<2>(a, h->batch, dyn, s); break;
-        case 3: launch<3>(a, h->batch, dyn, s); break;
-        case 4: launch<4>(a, h->batch, dyn, s); break;
-        case 5: launch<5>(a, h->batch, dyn, s); break;
-        default: return fail(AWE_ERR_ARG, "unsupported d");
-    }
+    if (int rc = for_degree<2>(L.d, [&](auto dc) -> int {
+            dual_interval_kernel<decltype(dc)::value><<<dim3((unsigned)(h->batch * a.n_k)), kBlock, dyn, s>>>(a);
+            return AWE_OK;
+        }, unsupported_d)) return rc;
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(h->ev[1], s));
     dual_finalize_kernel<<<dim3((unsigned)h->batch), 64, 0, s>>>(a);

@@ -53,8 +53,6 @@ using namespace dlt;
         }                                                                              \
     } while (0)
 
-constexpr int kMaxTan = 1024;
-static_assert(awe_dgen::kNTan[0] <= kMaxTan && awe_dgen::kNTan[1] <= kMaxTan, "slot table too small");
 constexpr int kRoles = awe_dgen::kRoles;
 constexpr int kObjRows = 3 + awe_dgen::kNDbp;   // per Radau node: power, beta_2, beta_3, dbp[kNDbp]
 constexpr int kCO = 2 * ADL_NX + ADL_NU + ADL_NZ;   // x, u, xdot, z of an interval
@@ -63,33 +61,10 @@ constexpr int kNodeWaves = 4;
 // the node kernel compiles ~35k generated statements; other d use the colour kernel of awedual.hip)
 constexpr int kGenD = 4;
 
-// destination count of every tangent slot (1, or d for the xdot directions of a Radau node) and its
-// first entry in the node's destination row; compile-time on the device (the generated code's slot
-// numbers are constants), built with the run-time d on the host
-struct SlotTab {
-    int first[2][kMaxTan];
-    int cnt[2][kMaxTan];
-    int total[2];
-    __host__ __device__ constexpr SlotTab(int d) : first(), cnt(), total() {
-        for (int kind = 0; kind < 2; ++kind) {
-            int dir_of[kMaxTan] = {};
-            for (int s = 0; s < kMaxTan; ++s) dir_of[s] = -1;
-            for (int r = 0; r < kRowPower; ++r)
-                for (int l = 0; l < kDirs; ++l)
-                    if (awe_dgen::kTanIdx[kind][r][l] >= 0) dir_of[awe_dgen::kTanIdx[kind][r][l]] = l;
-            int f = 0;
-            for (int s = 0; s < awe_dgen::kNTan[kind]; ++s) {
-                const bool xd = kind == 1 && dir_of[s] >= ADL_NX && dir_of[s] < 2 * ADL_NX;
-                first[kind][s] = f;
-                cnt[kind][s] = xd ? d : 1;
-                f += cnt[kind][s];
-            }
-            total[kind] = f;
-        }
-    }
-};
-template <int D>
-constexpr SlotTab kSlots{D};
+// the tangent slots of dual_nodejac.gen.hpp (im_tables.hpp)
+using Slots = im::SlotTraits<awe_dgen::kTanIdx, awe_dgen::kNTan, ADL_NX, 1024>;
+template <int D, int KIND>
+using JSink = im::JSink<Slots, D, KIND>;
 
 struct Args {
     awt::DevColl coll;
@@ -155,30 +130,6 @@ struct ThIn {
     __device__ __forceinline__ double operator[](int i) const { return im::at(p, row0 + (unsigned)i, ld8, lb); }
 };
 
-// tan[s] = v  ->  the J_g entries of slot s (dt: the node's destination row in LDS, byte offsets)
-template <int D, int KIND>
-struct JSink {
-    double* jac;
-    unsigned lb;
-    const unsigned* dt;
-    const double* xs;
-    struct Ref {
-        const JSink* s;
-        int slot;
-        __device__ __forceinline__ void operator=(double v) const { s->put(slot, v); }
-    };
-    __device__ __forceinline__ Ref operator[](int slot) const { return Ref{this, slot}; }
-    __device__ __forceinline__ void put(int slot, double v) const {
-        const int f = kSlots<D>.first[KIND][slot], c = kSlots<D>.cnt[KIND][slot];
-        if (c == 1) {
-            __builtin_nontemporal_store(v, &im::at_byte(jac, dt[f] + lb));
-            return;
-        }
-#pragma unroll
-        for (int q = 0; q < D; ++q) __builtin_nontemporal_store(xs[q] * v, &im::at_byte(jac, dt[f + q] + lb));
-    }
-};
-
 // rows r0 + i of an instance-minor buffer
 struct ImRef {
     double* p;
@@ -226,7 +177,7 @@ __device__ __forceinline__ void radau_tile(int t, unsigned* ldt, const double* _
                                            double* __restrict__ jac, double* __restrict__ objb, const Args& a) {
     constexpr int NN = D + 1;
     constexpr int W = D < kNodeWaves ? D : kNodeWaves;
-    constexpr int T1 = kSlots<D>.total[1];
+    constexpr int T1 = im::kSlots<Slots, D>.total[1];
     const int role = t % kRoles, tk = t / kRoles;
     const int ib = tk / a.n_k, k = tk - ib * a.n_k;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -278,7 +229,7 @@ __device__ __forceinline__ void shoot_tile(int t, unsigned* ldt, const double* _
                                            const int* __restrict__ coff, double* __restrict__ g,
                                            double* __restrict__ jac, const Args& a) {
     constexpr int NN = D + 1;
-    constexpr int T0 = kSlots<D>.total[0];
+    constexpr int T0 = im::kSlots<Slots, D>.total[0];
     const int nk4 = (a.n_k + kNodeWaves - 1) / kNodeWaves;
     const int role = t % kRoles, tk = t / kRoles;
     const int ib = tk / nk4, k0 = (tk - ib * nk4) * kNodeWaves;
@@ -312,7 +263,7 @@ void dual_gen_node_kernel(const double* __restrict__ VT, const double* __restric
                           const double* __restrict__ cst, const unsigned* __restrict__ dtab,
                           const unsigned* __restrict__ ctab, const int* __restrict__ coff, double* __restrict__ g,
                           double* __restrict__ jac, double* __restrict__ objb, Args a) {
-    constexpr int T0 = kSlots<D>.total[0], T1 = kSlots<D>.total[1];
+    constexpr int T0 = im::kSlots<Slots, D>.total[0], T1 = im::kSlots<Slots, D>.total[1];
     constexpr int NLDT = D * T1 > kNodeWaves * T0 ? D * T1 : kNodeWaves * T0;
     __shared__ unsigned ldt[NLDT];
     const int nr = a.nib * a.n_k * kRoles;
@@ -613,7 +564,7 @@ struct Plan {
 void destroy(Plan* p) { delete p; }
 
 // destination tables from the gather list of build_tables: per (interval k, node n) a row of CCS
-// positions in kSlots order (slot s of the node's generated code, then its d polynomial columns for a
+// positions in slot order (slot s of the node's generated code, then its d polynomial columns for a
 // Radau xdot direction), and per interval the constant entries (position | value index << 24)
 int create(const Tables& T, const std::vector<double>& consts, int batch, Plan** out, std::string& why,
            std::string& err) {
@@ -650,11 +601,7 @@ int create(const Tables& T, const std::vector<double>& consts, int batch, Plan**
                 if (T.dmask[kind][dir].has(r)) rev[kind][ct.off[kind][c] + m.below(r)] = {r, dir};
         }
     }
-    const SlotTab st(d);
-    const int dstride = std::max(st.total[0], st.total[1]);
-    std::vector<unsigned> dtab((size_t)n_k * NN * dstride, 0xffffffffu);
-    std::vector<unsigned> ctab;
-    std::vector<int> coff(n_k + 1, 0);
+    im::DestTables<Slots> tabs(n_k, d);
     auto fail_int = [&](const char* m) { err = m; return AWE_ERR_ARG; };
     for (int k = 0; k < n_k; ++k) {
         for (int e = T.goff[k]; e < T.goff[k + 1]; ++e) {
@@ -663,7 +610,7 @@ int create(const Tables& T, const std::vector<double>& consts, int batch, Plan**
             const uint32_t kind = cd >> 29;
             const int rr = (cd >> 25) & 15, nn = (cd >> 21) & 15, src = (int)(cd & ((1u << 21) - 1u));
             if (kind == kKindConst) {
-                ctab.push_back(pos | ((unsigned)src << 24));
+                tabs.add_const(k, pos, (unsigned)src);
                 continue;
             }
             // src = toff(n) + node-relative index; the poly code carries n, the plain one is found by range
@@ -675,21 +622,12 @@ int create(const Tables& T, const std::vector<double>& consts, int batch, Plan**
             if (r < 0) return fail_int("internal: gather entry without a (row, direction)");
             const int s = awe_dgen::kTanIdx[kd][r][dir];
             if (s < 0) return fail_int("internal: J_g entry without a generated tangent");
-            int q = 0;
-            if (kind == kKindTangPoly) q = rr < n ? rr : rr - 1;
-            if (q >= st.cnt[kd][s]) return fail_int("internal: destination count of a generated tangent");
-            unsigned& slot = dtab[(size_t)(k * NN + n) * dstride + st.first[kd][s] + q];
-            if (slot != 0xffffffffu) return fail_int("internal: two J_g entries for one generated destination");
-            slot = pos;
+            const int q = kind == kKindTangPoly ? (rr < n ? rr : rr - 1) : 0;
+            if (const char* why_not = tabs.place(k, n, kd, s, q, pos)) return fail_int(why_not);
         }
-        coff[k + 1] = (int)ctab.size();
-        for (int n = 0; n < NN; ++n)
-            for (int i = 0; i < st.total[n > 0 ? 1 : 0]; ++i)
-                if (dtab[(size_t)(k * NN + n) * dstride + i] == 0xffffffffu)
-                    return fail_int("internal: generated destination without a J_g entry");
+        tabs.close_interval(k);
     }
-    if (ctab.empty()) ctab.push_back(0);
-    for (auto& x : dtab) if (x == 0xffffffffu) x = 0;   // padding of the shorter node kind
+    if (const char* why_not = tabs.finish()) return fail_int(why_not);
     auto p = std::make_unique<Plan>();   // freed, with all it owns, by every early return
     Args& a = p->a;
     for (int j = 0; j < NN; ++j) {
@@ -706,7 +644,7 @@ int create(const Tables& T, const std::vector<double>& consts, int batch, Plan**
     a.v_int0 = L.v_int0;
     a.rows = L.rows;
     a.nib = (batch + 63) / 64;
-    a.dstride = dstride;
+    a.dstride = tabs.dstride;
     a.nkr = L.nk_reelout;
     a.single = L.single;
     a.n_thv = L.n_thv;
@@ -720,9 +658,9 @@ int create(const Tables& T, const std::vector<double>& consts, int batch, Plan**
         why = "instance-minor inputs would exceed 4 GiB";
         return AWE_OK;
     }
-    DGEN_TRY(p->d_dtab.upload(dtab));
-    DGEN_TRY(p->d_ctab.upload(ctab));
-    DGEN_TRY(p->d_coff.upload(coff));
+    DGEN_TRY(p->d_dtab.upload(tabs.dtab));
+    DGEN_TRY(p->d_ctab.upload(tabs.ctab));
+    DGEN_TRY(p->d_coff.upload(tabs.coff));
     DGEN_TRY(p->d_VT.alloc(p->ld * L.n_v));
     DGEN_TRY(p->d_PT.alloc(p->ld * L.n_p));
     DGEN_TRY(p->d_objb.alloc(p->ld * (size_t)n_k * d * kObjRows));

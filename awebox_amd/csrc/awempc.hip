@@ -489,36 +489,10 @@ __global__ __launch_bounds__(64) void mpc_hess_finalize_kernel(HArgs ha) {
 // J_g and grad f leave instance-minor (jac[e * ldj + b]), every store one 512-byte row; g stays
 // per-instance (g[b * n_g + i]) as the solver reads it.
 // ---------------------------------------------------------------------------------------------
-constexpr int kGenMaxTan = 128;
-static_assert(awe_k3gen::kNTan[0] <= kGenMaxTan && awe_k3gen::kNTan[1] <= kGenMaxTan, "slot table too small");
-
-// destination count of every tangent slot (1, or d for the xdot directions of a Radau node) and its
-// first entry in the node's destination row; compile-time on the device (the generated code's slot
-// numbers are constants), built with the run-time d on the host
-struct GenSlotTab {
-    int first[2][kGenMaxTan];
-    int cnt[2][kGenMaxTan];
-    int total[2];
-    __host__ __device__ constexpr GenSlotTab(int d) : first(), cnt(), total() {
-        for (int kind = 0; kind < 2; ++kind) {
-            int dir_of[kGenMaxTan] = {};
-            for (int s = 0; s < kGenMaxTan; ++s) dir_of[s] = -1;
-            for (int r = 0; r < kRowsPerNode; ++r)
-                for (int l = 0; l < kLanes; ++l)
-                    if (awe_k3gen::kTanIdx[kind][r][l] >= 0) dir_of[awe_k3gen::kTanIdx[kind][r][l]] = l;
-            int f = 0;
-            for (int s = 0; s < awe_k3gen::kNTan[kind]; ++s) {
-                const bool xd = kind == 1 && dir_of[s] >= K3_NX && dir_of[s] < 2 * K3_NX;
-                first[kind][s] = f;
-                cnt[kind][s] = xd ? d : 1;
-                f += cnt[kind][s];
-            }
-            total[kind] = f;
-        }
-    }
-};
-template <int D>
-constexpr GenSlotTab kGenSlots{D};
+// the tangent slots of kite3_nodejac.gen.hpp (im_tables.hpp)
+using GenSlots = im::SlotTraits<awe_k3gen::kTanIdx, awe_k3gen::kNTan, K3_NX, 128>;
+template <int D, int KIND>
+using GenJSink = im::JSink<GenSlots, D, KIND>;
 
 struct GenArgs {
     awt::DevColl coll;
@@ -560,30 +534,6 @@ struct GenIn {
         if (i < 2 * K3_NX + K3_NU) return at(c0 + K3_NX + (i - 2 * K3_NX));   // u[k], zero-order hold
         if (i < K3_NW) return at(i - (2 * K3_NX + K3_NU + K3_NZ));             // theta: diam_t, t_f
         return at(K3_NTH + 0);                                                 // phi.gamma
-    }
-};
-
-// tan[s] = v  ->  the J_g entries of slot s (dt: the node's destination row in LDS, byte offsets)
-template <int D, int KIND>
-struct GenJSink {
-    double* jac;
-    unsigned lb;
-    const unsigned* dt;
-    const double* xs;
-    struct Ref {
-        const GenJSink* s;
-        int slot;
-        __device__ __forceinline__ void operator=(double v) const { s->put(slot, v); }
-    };
-    __device__ __forceinline__ Ref operator[](int slot) const { return Ref{this, slot}; }
-    __device__ __forceinline__ void put(int slot, double v) const {
-        const int f = kGenSlots<D>.first[KIND][slot], c = kGenSlots<D>.cnt[KIND][slot];
-        if (c == 1) {
-            __builtin_nontemporal_store(v, &im::at_byte(jac, dt[f] + lb));
-            return;
-        }
-#pragma unroll
-        for (int q = 0; q < D; ++q) __builtin_nontemporal_store(xs[q] * v, &im::at_byte(jac, dt[f + q] + lb));
     }
 };
 
@@ -632,7 +582,7 @@ __device__ __forceinline__ void gen_radau_tile(int t, unsigned* ldt, const doubl
                                                double* __restrict__ jac, const GenArgs& a) {
     constexpr int NN = D + 1;
     constexpr int W = gen_radau_waves<D>();
-    constexpr int T1 = kGenSlots<D>.total[1];
+    constexpr int T1 = im::kSlots<GenSlots, D>.total[1];
     const int sg = t % kGenStripGroups, tk = t / kGenStripGroups;
     const int ib = tk / a.n_k, k = tk - ib * a.n_k;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -698,7 +648,7 @@ __device__ __forceinline__ void gen_shoot_tile(int t, unsigned* ldt, const doubl
                                                double* __restrict__ grad, double* __restrict__ jac,
                                                double* __restrict__ fpart, const GenArgs& a) {
     constexpr int NN = D + 1;
-    constexpr int T0 = kGenSlots<D>.total[0];
+    constexpr int T0 = im::kSlots<GenSlots, D>.total[0];
     const int nk4 = (a.n_k + kGenShootWaves - 1) / kGenShootWaves;
     const int sg = t % kGenStripGroups, tk = t / kGenStripGroups;
     const int ib = tk / nk4, k0 = (tk - ib * nk4) * kGenShootWaves;
@@ -815,7 +765,7 @@ void mpc_gen_node_kernel(const double* __restrict__ VT, const double* __restrict
                          const double* __restrict__ cst, const unsigned* __restrict__ dtab,
                          const unsigned* __restrict__ ctab, const int* __restrict__ coff, double* __restrict__ g,
                          double* __restrict__ grad, double* __restrict__ jac, double* __restrict__ fpart, GenArgs a) {
-    constexpr int T0 = kGenSlots<D>.total[0], T1 = kGenSlots<D>.total[1];
+    constexpr int T0 = im::kSlots<GenSlots, D>.total[0], T1 = im::kSlots<GenSlots, D>.total[1];
     constexpr int NLDT = D * T1 > kGenShootWaves * T0 ? D * T1 : kGenShootWaves * T0;
     __shared__ unsigned ldt[NLDT];
     const int nr = gen_radau_tiles<D>(a);
@@ -904,8 +854,10 @@ struct awempc_handle_s {
 
 namespace {
 
+int unsupported_d() { return fail(AWE_ERR_ARG, "unsupported d"); }
+
 // destination tables of the generated path from the gather list of build_tables: per (interval k,
-// node n) a row of CCS positions in kGenSlots order (slot s of the node's generated code, then its
+// node n) a row of CCS positions in slot order (slot s of the node's generated code, then its
 // d polynomial columns for a Radau xdot direction), and per interval the constant entries
 // (position | value index << 24, values 1, -D[r])
 int build_gen(awempc_handle_s* h) {
@@ -917,11 +869,7 @@ int build_gen(awempc_handle_s* h) {
         return AWE_OK;
     }
     if ((size_t)T.row.size() >= (1u << 24)) { h->gen_why = "J_g too large for the constant table"; return AWE_OK; }
-    const GenSlotTab st(d);
-    const int dstride = std::max(st.total[0], st.total[1]);
-    std::vector<unsigned> dtab((size_t)n_k * NN * dstride, 0xffffffffu);
-    std::vector<unsigned> ctab;
-    std::vector<int> coff(n_k + 1, 0);
+    im::DestTables<GenSlots> tabs(n_k, d);
     for (int k = 0; k < n_k; ++k) {
         for (int e = T.goff[k]; e < T.goff[k + 1]; ++e) {
             const unsigned pos = (unsigned)T.gslot[e];
@@ -929,35 +877,26 @@ int build_gen(awempc_handle_s* h) {
             const uint32_t kind = cd >> 29;
             const int rr = (cd >> 25) & 15, idx = (int)(cd & ((1u << 21) - 1u));
             if (kind == kKindOne || kind == kKindMinusD) {
-                ctab.push_back(pos | ((kind == kKindOne ? 0u : 1u + (unsigned)rr) << 24));
+                tabs.add_const(k, pos, kind == kKindOne ? 0u : 1u + (unsigned)rr);
                 continue;
             }
             const int n = idx / (kRowsPerNode * kLanes), r = (idx / kLanes) % kRowsPerNode, l = idx % kLanes;
             const int kd = n > 0 ? 1 : 0;
             const int s = awe_k3gen::kTanIdx[kd][r][l];
             if (s < 0) return fail(AWE_ERR_ARG, "internal: J_g entry without a generated tangent");
-            int q = 0;
-            if (kind == kKindTangPoly) q = rr < n ? rr : rr - 1;
-            if (q >= st.cnt[kd][s]) return fail(AWE_ERR_ARG, "internal: destination count of a generated tangent");
-            unsigned& slot = dtab[(size_t)(k * NN + n) * dstride + st.first[kd][s] + q];
-            if (slot != 0xffffffffu) return fail(AWE_ERR_ARG, "internal: two J_g entries for one generated destination");
-            slot = pos;
+            const int q = kind == kKindTangPoly ? (rr < n ? rr : rr - 1) : 0;
+            if (const char* why = tabs.place(k, n, kd, s, q, pos)) return fail(AWE_ERR_ARG, why);
         }
-        coff[k + 1] = (int)ctab.size();
-        for (int n = 0; n < NN; ++n)
-            for (int i = 0; i < st.total[n > 0 ? 1 : 0]; ++i)
-                if (dtab[(size_t)(k * NN + n) * dstride + i] == 0xffffffffu)
-                    return fail(AWE_ERR_ARG, "internal: generated destination without a J_g entry");
+        tabs.close_interval(k);
     }
-    if (ctab.empty()) ctab.push_back(0);
-    for (auto& x : dtab) if (x == 0xffffffffu) x = 0;   // padding of the shorter node kind
+    if (const char* why = tabs.finish()) return fail(AWE_ERR_ARG, why);
     h->gen_kconst[0] = 1.0;
     for (int r = 0; r < NN; ++r) h->gen_kconst[1 + r] = -h->t.coll.D[r];
-    h->gen_dstride = dstride;
+    h->gen_dstride = tabs.dstride;
     h->gen_ld = (size_t)h->batch;
-    HIP_TRY(h->d_gdtab.upload(dtab));
-    HIP_TRY(h->d_gctab.upload(ctab));
-    HIP_TRY(h->d_gcoff.upload(coff));
+    HIP_TRY(h->d_gdtab.upload(tabs.dtab));
+    HIP_TRY(h->d_gctab.upload(tabs.ctab));
+    HIP_TRY(h->d_gcoff.upload(tabs.coff));
     HIP_TRY(h->d_VT.alloc(h->gen_ld * T.lay.n_v));
     HIP_TRY(h->d_PT.alloc(h->gen_ld * T.lay.n_p));
     HIP_TRY(h->d_gfpart.alloc(h->gen_ld * n_k));
@@ -1042,13 +981,11 @@ int awempc_eval_nlp(awempc_handle h, const double* V, const double* p, double* f
             V, p, f, g, grad_f, jac, h->d_cst, h->d_coll, h->d_goff, h->d_gslot, h->d_gcode, h->d_fpart};
     const dim3 grid((unsigned)(h->batch * T.lay.n_k));
     HIP_TRY(hipEventRecord(h->ev[0], s));
-    switch (T.lay.d) {
-        case 2: mpc_interval_kernel<2><<<grid, 64 * waves_for<2>(), 0, s>>>(a); break;
-        case 3: mpc_interval_kernel<3><<<grid, 64 * waves_for<3>(), 0, s>>>(a); break;
-        case 4: mpc_interval_kernel<4><<<grid, 64 * waves_for<4>(), 0, s>>>(a); break;
-        case 5: mpc_interval_kernel<5><<<grid, 64 * waves_for<5>(), 0, s>>>(a); break;
-        default: return fail(AWE_ERR_ARG, "unsupported d");
-    }
+    if (int rc = for_degree<2>(T.lay.d, [&](auto dc) -> int {
+            constexpr int D = decltype(dc)::value;
+            mpc_interval_kernel<D><<<grid, 64 * waves_for<D>(), 0, s>>>(a);
+            return AWE_OK;
+        }, unsupported_d)) return rc;
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(h->ev[1], s));
     mpc_finalize_kernel<<<dim3((unsigned)h->batch), 64, 0, s>>>(a);
@@ -1105,17 +1042,11 @@ int awempc_eval_nlp_im(awempc_handle h, const double* V, const double* p, double
     const int n_tiles = a.nib * (a.n_k + (a.n_k + kGenShootWaves - 1) / kGenShootWaves) * kGenStripGroups +
                         (AWE_MPC_EXTRA_TILES ? a.nib * ((a.n_k + kGenShootWaves - 1) / kGenShootWaves) : 0);
     const dim3 ngrid((unsigned)im::xcd_grid(n_tiles));
-#define MPC_GEN_NODE(DD)                                                                                           \
-    mpc_gen_node_kernel<DD><<<ngrid, 64 * kGenNodeWaves, 0, s>>>(h->d_VT, h->d_PT, h->d_cst, h->d_gdtab, h->d_gctab, \
-                                                                 h->d_gcoff, g, grad_f, jac, h->d_gfpart, a)
-    switch (T.lay.d) {
-        case 2: MPC_GEN_NODE(2); break;
-        case 3: MPC_GEN_NODE(3); break;
-        case 4: MPC_GEN_NODE(4); break;
-        case 5: MPC_GEN_NODE(5); break;
-        default: return fail(AWE_ERR_ARG, "unsupported d");
-    }
-#undef MPC_GEN_NODE
+    if (int rc = for_degree<2>(T.lay.d, [&](auto dc) -> int {
+            mpc_gen_node_kernel<decltype(dc)::value><<<ngrid, 64 * kGenNodeWaves, 0, s>>>(
+                h->d_VT, h->d_PT, h->d_cst, h->d_gdtab, h->d_gctab, h->d_gcoff, g, grad_f, jac, h->d_gfpart, a);
+            return AWE_OK;
+        }, unsupported_d)) return rc;
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(h->gev[2], s));
     mpc_gen_finalize_kernel<<<dim3((unsigned)a.nib), 64, 0, s>>>(h->d_VT, h->d_PT, h->d_gfpart, f, grad_f, a);
@@ -1215,13 +1146,10 @@ int awempc_eval_hess(awempc_handle h, const double* V, const double* p, const do
     const dim3 grid((unsigned)(h->batch * T.lay.n_k));
     const size_t lds = sizeof(double) * (size_t)h->hd_total;
     HIP_TRY(hipEventRecord(h->hev[0], s));
-    switch (T.lay.d) {
-        case 2: mpc_hess_kernel<2><<<grid, kHessThreads, lds, s>>>(ha); break;
-        case 3: mpc_hess_kernel<3><<<grid, kHessThreads, lds, s>>>(ha); break;
-        case 4: mpc_hess_kernel<4><<<grid, kHessThreads, lds, s>>>(ha); break;
-        case 5: mpc_hess_kernel<5><<<grid, kHessThreads, lds, s>>>(ha); break;
-        default: return fail(AWE_ERR_ARG, "unsupported d");
-    }
+    if (int rc = for_degree<2>(T.lay.d, [&](auto dc) -> int {
+            mpc_hess_kernel<decltype(dc)::value><<<grid, kHessThreads, lds, s>>>(ha);
+            return AWE_OK;
+        }, unsupported_d)) return rc;
     HIP_TRY(hipGetLastError());
     mpc_hess_finalize_kernel<<<dim3((unsigned)h->batch), 64, 0, s>>>(ha);
     HIP_TRY(hipGetLastError());

@@ -11,6 +11,7 @@
 #include <cstring>
 #include <initializer_list>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -116,6 +117,15 @@ inline bool all_finite(const double* x, size_t n) {
     for (size_t i = 0; i < n; ++i)
         if (!std::isfinite(x[i])) return false;
     return true;
+}
+
+// The collocation degree as a compile-time constant: f(std::integral_constant<int, D>{}) for the D in
+// LO..5 that equals the run-time d, and its result; for any other d, unsupported() and its result.
+template <int LO = 1, class F, class U>
+auto for_degree(int d, F&& f, U&& unsupported) -> decltype(unsupported()) {
+    if constexpr (LO > 5) return unsupported();
+    else if (d == LO) return f(std::integral_constant<int, LO>{});
+    else return for_degree<LO + 1>(d, f, unsupported);
 }
 
 // One array of a host round trip: the handle's staging buffer, the caller's array and its length.
