@@ -3,7 +3,9 @@ update Bunch-Kaufman logic on the CPU before it runs on the GPU: the same storag
 triangle kept column-major, i.e. in the upper triangle of the row-major array), the same panel
 bookkeeping (W = L D columns, the L coefficients of each column, the symmetric interchanges applied
 to the un-updated trailing matrix) and the same decisions; the counts are compared with eigenvalue
-counts.  Not used by the product or the tests."""
+counts.  Not used by the product; tests/test_inertia_model.py runs inertia_blocked on the structured
+families of tests/awelu_cases.py (saddle points, exact ties, exact zeros) at panel widths 4, 7 and
+16, so that the GPU tests' inputs are ones on which the algorithm itself is known to be right."""
 import numpy as np
 
 ALPHA = (1.0 + np.sqrt(17.0)) / 8.0
