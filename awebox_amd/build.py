@@ -11,8 +11,9 @@ travel with the repository snapshot to the GPU box.
 Before the libraries are compiled, ``generate()`` refreshes the generated node code: each node model
 is traced and differentiated by its generator under ``csrc/gen/`` (g++, host) for the default
 constants -- ``ap2_nodejac.gen.hpp`` / ``ap2_nodehess.gen.hpp`` (AP2 Jacobian and Hessian),
-``kite3_nodejac.gen.hpp`` (tracking MPC), ``dual_nodejac.gen.hpp`` (dual kites) -- and the straight-line
-code they write is what the instance-minor kernels run.
+``kite3_nodejac.gen.hpp`` (tracking MPC), ``kite3_noderoot.gen.hpp`` (its plant's rootfinder),
+``dual_nodejac.gen.hpp`` (dual kites) -- and the straight-line code they write is what the
+instance-minor kernels run.
 """
 from __future__ import annotations
 
@@ -39,6 +40,9 @@ K3_HEADER = os.path.join(CSRC, "kite3_nodejac.gen.hpp")
 K3_SOURCES = [os.path.join(CSRC, "gen", f) for f in ("kite3_jacgen.cpp", "sym.hpp")] + [
     os.path.join(CSRC, f) for f in ("kite3_model.hpp", "kite3_tables.hpp", "ap2_tables.hpp", "scalar.hpp")] + [
     os.path.join(INCLUDE, "awempc.h"), os.path.join(INCLUDE, "awegpu.h"), os.path.join(HERE, "kite3.py")]
+# the 3-DOF plant's rootfinder node code (csrc/gen/kite3_rootgen.cpp): the inputs of K3_SOURCES
+K3_ROOT_HEADER = os.path.join(CSRC, "kite3_noderoot.gen.hpp")
+K3_ROOT_SOURCES = [os.path.join(CSRC, "gen", "kite3_rootgen.cpp")] + K3_SOURCES[1:]
 # the dual-kite node-Jacobian code (csrc/gen/dual_jacgen.cpp)
 DUAL_HEADER = os.path.join(CSRC, "dual_nodejac.gen.hpp")
 DUAL_SOURCES = [os.path.join(CSRC, "gen", f) for f in ("dual_jacgen.cpp", "sym.hpp")] + [
@@ -47,7 +51,8 @@ DUAL_SOURCES = [os.path.join(CSRC, "gen", f) for f in ("dual_jacgen.cpp", "sym.h
     os.path.join(INCLUDE, "awedual.h"), os.path.join(INCLUDE, "awegpu.h"), os.path.join(HERE, "dual.py")]
 # (header, generator source, inputs hashed into the header's first line, default constants)
 GENERATORS = [(GEN_HEADER, "ap2_jacgen.cpp", GEN_SOURCES, "ap2"), (HESS_HEADER, "ap2_hessgen.cpp", HESS_SOURCES, "ap2"),
-              (K3_HEADER, "kite3_jacgen.cpp", K3_SOURCES, "kite3"), (DUAL_HEADER, "dual_jacgen.cpp", DUAL_SOURCES, "dual")]
+              (K3_HEADER, "kite3_jacgen.cpp", K3_SOURCES, "kite3"),
+              (K3_ROOT_HEADER, "kite3_rootgen.cpp", K3_ROOT_SOURCES, "kite3"), (DUAL_HEADER, "dual_jacgen.cpp", DUAL_SOURCES, "dual")]
 # content hash of GEN_SOURCES recorded in the generated header's first line: the header is stale
 # when the hash differs (file times do not survive a checkout or the copy to the GPU box)
 _HASH_TAG = "// inputs-sha1: "
@@ -57,8 +62,9 @@ _COMMON = [os.path.join(CSRC, f) for f in ("ap2_model.hpp", "ap2_tables.hpp", "s
 TARGETS = {
     LIB: ([os.path.join(CSRC, "awegpu.hip")], _COMMON + [GEN_HEADER, HESS_HEADER]),
     LIB_MPC: ([os.path.join(CSRC, "awempc.hip")],
-              _COMMON + [os.path.join(CSRC, f) for f in ("kite3_model.hpp", "kite3_tables.hpp")]
-              + [os.path.join(INCLUDE, "awempc.h"), K3_HEADER]),
+              _COMMON + [os.path.join(CSRC, f) for f in ("kite3_model.hpp", "kite3_tables.hpp",
+                                                         "plant_rk4root.hpp")]
+              + [os.path.join(INCLUDE, "awempc.h"), K3_HEADER, K3_ROOT_HEADER]),
     LIB_DUAL: ([os.path.join(CSRC, "awedual.hip"), os.path.join(CSRC, "awedual_gen.hip")],
                _COMMON + [os.path.join(CSRC, f) for f in ("dual_model.hpp", "dual_tables.hpp", "dual_hess_tables.hpp",
                                                           "awedual_gen.hpp")]

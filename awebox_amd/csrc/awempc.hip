@@ -28,7 +28,9 @@
 #include "im_layout.hpp"
 #include "kite3_model.hpp"
 #include "kite3_nodejac.gen.hpp"
+#include "kite3_noderoot.gen.hpp"
 #include "kite3_tables.hpp"
+#include "plant_rk4root.hpp"
 
 namespace {
 
@@ -815,6 +817,138 @@ __global__ __launch_bounds__(64) void mpc_gen_finalize_kernel(const double* __re
     f[b] = s;
 }
 
+// ---------------------------------------------------------------------------------------------
+// The reference's simulation plant (sim.py:72-78 -> rk4root, tools/integrator_routines.py:32-96):
+// plant_rk4root.hpp instantiated on the generated rootfinder node code (kite3_noderoot.gen.hpp).
+//   mpc_plant_rk4root_kernel: one lane per loop, one launch for all n_steps sampling times, no
+//   cross-lane operation.  A lane's 12 x 12 matrix and right-hand side sit in LDS lane-minor (entry e
+//   of lane l at [e * 64 + l]: every lane of a ds_read_b64 / ds_write_b64 in its own bank pair whatever
+//   row it pivots on), 72 + 6 KiB, so one wavefront per workgroup; the constants and the xdot / x
+//   scaling ratios are staged once behind them.  awempc_plant_rk4root_cpu runs the same core on the host.
+// ---------------------------------------------------------------------------------------------
+constexpr int kPlantN = awe_k3root::kNUnk;               // 12 unknowns (xdot, z) = 12 rows
+constexpr int kPlantPar = 4;                             // theta.diam_t, theta.t_f, phi.gamma, u_ref
+static_assert(awe_k3root::kNRows == kPlantN && kPlantN == K3_NX + K3_NZ, "square rootfinder system");
+
+// node inputs of the generated code from the stage state, the unknowns, the applied control and par
+struct PlantIn {
+    const double* x;
+    const double* y;
+    const double* u;
+    const double* par;
+    AWE_HD double operator()(int i) const {
+        if (i < K3_NX) return x[i];
+        if (i < 2 * K3_NX) return y[i - K3_NX];
+        if (i < 2 * K3_NX + K3_NU) return u[i - 2 * K3_NX];
+        if (i == awe::k3::Z_LAMBDA) return y[K3_NX];
+        return par[i - (awe::k3::Z_LAMBDA + 1)];          // theta.diam_t, theta.t_f, phi.gamma
+    }
+};
+
+template <class Sys>
+struct PlantRows {
+    Sys& sys;
+    AWE_HD double& operator[](int r) const { return sys.r(r); }
+};
+template <class Sys>
+struct PlantSlots {
+    Sys& sys;
+    AWE_HD double& operator[](int s) const {
+        return sys.a(awe_k3root::kEntry[s] / kPlantN, awe_k3root::kEntry[s] % kPlantN);
+    }
+};
+
+// plant_rk4root.hpp's Node for the 3-DOF kite; cst: the model constants followed by the K3_NX ratios
+// s[xdot_i] / s[x_i], u: the loop's controls [n_steps][K3_NU], par: its kPlantPar parameters
+struct K3PlantNode {
+    const double* cst;
+    const double* u_seq;
+    double par[kPlantPar];
+    double u[K3_NU];
+    AWE_HD void begin(int step) {
+#pragma unroll
+        for (int i = 0; i < K3_NU; ++i) u[i] = u_seq[(size_t)step * K3_NU + i];
+    }
+    template <class Sys>
+    AWE_HD void eval(int, const double* x, const double* y, Sys& sys) const {
+#pragma unroll
+        for (int r = 0; r < kPlantN; ++r)
+#pragma unroll
+            for (int j = 0; j < kPlantN; ++j)
+                if (awe_k3root::kSlot[r][j] < 0) sys.a(r, j) = 0.0;      // the LU fills in: rewritten every time
+        awe_k3root::k3_node_root<1>(PlantIn{x, y, u, par}, par[3], cst, PlantRows<Sys>{sys}, PlantSlots<Sys>{sys});
+    }
+    // the power integral's integrand lambda l_t dl_t in SI units (dynamics.py:318-330)
+    AWE_HD double integrand(int, const double* x, const double* y) const {
+        const double* s = cst + K3_C_SCALING;
+        return (y[K3_NX] * s[awe::k3::Z_LAMBDA]) * (x[awe::k3::LT] * s[awe::k3::LT]) * (x[awe::k3::DLT] * s[awe::k3::DLT]);
+    }
+    AWE_HD double rate(int i, double xdot_scaled) const { return xdot_scaled * cst[K3_NCONST + i]; }
+};
+
+struct PlantLdsSys {       // both pointers already at the lane's column
+    double* A;
+    double* b;
+    __device__ __forceinline__ double& a(int i, int j) const { return A[(i * kPlantN + j) * 64]; }
+    __device__ __forceinline__ double& r(int i) const { return b[i * 64]; }
+};
+struct PlantHostSys {
+    double A[kPlantN * kPlantN], b[kPlantN];
+    double& a(int i, int j) { return A[i * kPlantN + j]; }
+    double& r(int i) { return b[i]; }
+};
+
+struct PlantArgs {
+    const double* x0;     // [B][K3_NX]
+    const double* u;      // [B][n_steps][K3_NU]
+    const double* z0;     // [B][kPlantN]
+    const double* par;    // [B][kPlantPar]
+    const double* cst;    // [K3_NCONST]
+    double ts, tol;
+    int n_fe, n_steps, max_newton, batch;
+    double* xf;           // [B][n_steps][K3_NX]
+    double* zf;           // [B][kPlantN]
+    double* qf;           // [B][n_steps]
+    double* res;          // [B]
+};
+
+// one instance of the plant; shared by the kernel's lanes and the host loop
+template <class Sys>
+AWE_HD void plant_instance(const PlantArgs& a, size_t b, const double* cst_ratio, Sys& sys) {
+    K3PlantNode node{cst_ratio, a.u + b * (size_t)a.n_steps * K3_NU, {}, {}};
+    double x[K3_NX], y[kPlantN];
+#pragma unroll
+    for (int i = 0; i < kPlantPar; ++i) node.par[i] = a.par[b * kPlantPar + i];
+#pragma unroll
+    for (int i = 0; i < K3_NX; ++i) x[i] = a.x0[b * K3_NX + i];
+#pragma unroll
+    for (int i = 0; i < kPlantN; ++i) y[i] = a.z0[b * kPlantN + i];
+    double* xf = a.xf + b * (size_t)a.n_steps * K3_NX;
+    double* qf = a.qf + b * (size_t)a.n_steps;
+    const double res = awe::rk4root_run<K3_NX, kPlantN>(
+        node, sys, x, y, a.ts, a.n_fe, a.n_steps, a.max_newton, a.tol,
+        [xf](int s, int i, double v) { xf[(size_t)s * K3_NX + i] = v; }, [qf](int s, double v) { qf[s] = v; });
+#pragma unroll
+    for (int i = 0; i < kPlantN; ++i) a.zf[b * kPlantN + i] = y[i];
+    a.res[b] = res;
+}
+
+__global__ __launch_bounds__(64) void mpc_plant_rk4root_kernel(PlantArgs a) {
+    __shared__ double A[kPlantN * kPlantN * 64];
+    __shared__ double rhs[kPlantN * 64];
+    __shared__ double cs[K3_NCONST + K3_NX];
+    const int lane = threadIdx.x;
+    if (lane < K3_NCONST) cs[lane] = a.cst[lane];
+    static_assert(K3_NCONST <= 64, "one wavefront stages the constants");
+    __syncthreads();
+    if (lane < K3_NX) cs[K3_NCONST + lane] = cs[K3_C_SCALING + K3_NX + lane] / cs[K3_C_SCALING + lane];
+    __syncthreads();
+    const size_t b = (size_t)blockIdx.x * 64 + lane;
+    if (b >= (size_t)a.batch) return;
+    PlantLdsSys sys{A + lane, rhs + lane};
+    plant_instance(a, b, cs, sys);
+}
+
 }  // namespace
 
 struct awempc_handle_s {
@@ -850,6 +984,9 @@ struct awempc_handle_s {
     double gen_kconst[8] = {};
     Event gev[4];
     bool gtimed = false;
+    // rk4root plant (awempc_plant_rk4root)
+    Event pev[2];
+    bool ptimed = false;
 };
 
 namespace {
@@ -947,6 +1084,7 @@ int awempc_create(int n_k, int d, const double* consts, int n_consts, int batch,
     HIP_TRY(h->d_gcode.upload(T.gcode));
     HIP_TRY(h->d_fpart.alloc((size_t)batch * n_k));
     for (auto& e : h->ev) HIP_TRY(e.create());
+    for (auto& e : h->pev) HIP_TRY(e.create());
     if (int rc = build_gen(h.get())) return rc;
     *out = h.release();
     return AWE_OK;
@@ -1083,6 +1221,61 @@ int awempc_eval_nlp_host(awempc_handle h, const double* V, const double* p, doub
         {{h->d_f, f, nb}, {h->d_g, g, nb * T.lay.n_g}, {h->d_grad, grad_f, nb * T.lay.n_v}, {h->d_jac, jac, nb * nnz}},
         [&] { return awempc_eval_nlp(h, h->d_V, h->d_P, h->d_f, h->d_g, h->d_grad, h->d_jac, nullptr); },
         "non-finite output");
+}
+
+// ---- rk4root plant ---------------------------------------------------------------------------
+static int plant_check(const double* consts, int n_consts, const void* const* ptrs, int n_ptrs, int batch, int n_fe,
+                       int n_steps, int max_newton) {
+    if (n_consts != K3_NCONST) return fail(AWE_ERR_ARG, "expected " + std::to_string(K3_NCONST) + " model constants");
+    if (batch < 1) return fail(AWE_ERR_ARG, "batch must be >= 1");
+    if (n_fe < 1) return fail(AWE_ERR_ARG, "n_fe must be >= 1");
+    if (n_steps < 1) return fail(AWE_ERR_ARG, "n_steps must be >= 1");
+    if (max_newton < 0) return fail(AWE_ERR_ARG, "max_newton must be >= 0");
+    for (int i = 0; i < n_ptrs; ++i)
+        if (!ptrs[i]) return fail(AWE_ERR_ARG, "null argument");
+    if ((int)consts[K3_C_N_ELEMENTS] != awe_k3root::kNElements)
+        return fail(AWE_ERR_ARG, "the generated rootfinder code has " + std::to_string(awe_k3root::kNElements) +
+                                     " tether elements, the constants " + std::to_string((int)consts[K3_C_N_ELEMENTS]));
+    return AWE_OK;
+}
+
+int awempc_plant_rk4root(awempc_handle h, const double* x0, const double* u, const double* z0, const double* par,
+                         double ts, int n_fe, int n_steps, int max_newton, double tol, double* xf, double* zf,
+                         double* qf, double* res, void* stream) {
+    if (!h) return fail(AWE_ERR_ARG, "null handle");
+    const void* ptrs[] = {x0, u, z0, par, xf, zf, qf, res};
+    if (int rc = plant_check(h->consts.data(), (int)h->consts.size(), ptrs, 8, h->batch, n_fe, n_steps, max_newton))
+        return rc;
+    hipStream_t s = (hipStream_t)stream;
+    PlantArgs a{x0, u, z0, par, h->d_cst, ts, tol, n_fe, n_steps, max_newton, h->batch, xf, zf, qf, res};
+    HIP_TRY(hipEventRecord(h->pev[0], s));
+    mpc_plant_rk4root_kernel<<<dim3((unsigned)((h->batch + 63) / 64)), 64, 0, s>>>(a);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(h->pev[1], s));
+    h->ptimed = true;
+    return AWE_OK;
+}
+
+int awempc_plant_rk4root_cpu(const double* consts, int n_consts, int batch, const double* x0, const double* u,
+                             const double* z0, const double* par, double ts, int n_fe, int n_steps, int max_newton,
+                             double tol, double* xf, double* zf, double* qf, double* res) {
+    const void* ptrs[] = {consts, x0, u, z0, par, xf, zf, qf, res};
+    if (!consts) return fail(AWE_ERR_ARG, "null argument");
+    if (int rc = plant_check(consts, n_consts, ptrs, 9, batch, n_fe, n_steps, max_newton)) return rc;
+    double cs[K3_NCONST + K3_NX];
+    for (int i = 0; i < K3_NCONST; ++i) cs[i] = consts[i];
+    for (int i = 0; i < K3_NX; ++i) cs[K3_NCONST + i] = cs[K3_C_SCALING + K3_NX + i] / cs[K3_C_SCALING + i];
+    PlantArgs a{x0, u, z0, par, cs, ts, tol, n_fe, n_steps, max_newton, batch, xf, zf, qf, res};
+    PlantHostSys sys;
+    for (int b = 0; b < batch; ++b) plant_instance(a, (size_t)b, cs, sys);
+    return AWE_OK;
+}
+
+int awempc_last_plant_ms(awempc_handle h, float* ms) {
+    if (!h || !h->ptimed) return fail(AWE_ERR_ARG, "no timed plant call yet");
+    HIP_TRY(hipEventSynchronize(h->pev[1]));
+    if (ms) HIP_TRY(hipEventElapsedTime(ms, h->pev[0], h->pev[1]));
+    return AWE_OK;
 }
 
 // ---- nlp_hess_l ------------------------------------------------------------------------------

@@ -10,11 +10,14 @@ There is no CPU fallback: a missing library or device raises ``AwegpuUnavailable
 """
 from __future__ import annotations
 
+import ctypes
 import os
+
+import numpy as np
 
 from . import kite3 as k3
 from . import nlp_binding as nb
-from .nlp_binding import FP, IP, H
+from .nlp_binding import DP, FP, IP, VP, H, I
 
 _LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libawempc.so")
 PREFIX = "awempc_"
@@ -22,7 +25,13 @@ SIGNATURES = {
     "hess_init": [H, IP],
     "gen_status": [H, IP],
     "last_kernel_ms_im": [H] + [FP] * 3,
+    # x0, u, z0, par | ts, n_fe, n_steps, max_newton, tol | xf, zf, qf, res
+    "plant_rk4root": [H] + [VP] * 4 + [ctypes.c_double, I, I, I, ctypes.c_double] + [VP] * 4 + [VP],
+    "plant_rk4root_cpu": [DP, I, I] + [DP] * 4 + [ctypes.c_double, I, I, I, ctypes.c_double] + [DP] * 4,
+    "last_plant_ms": [H, FP],
 }
+PLANT_NUNK = k3.NX + k3.NZ        # the rootfinder's unknowns: xdot (11), z.lambda
+PLANT_NPAR = 4                    # theta.diam_t, theta.t_f, phi.gamma (scaled), u_ref
 EXPORTED_SYMBOLS = nb.exported(PREFIX, SIGNATURES)
 
 
@@ -44,6 +53,28 @@ def sparsity_hess_static(consts: k3.Kite3Constants):
     return nb.static_sparsity(load_library(), PREFIX, "hess", consts, _n_v(consts))
 
 
+def plant_rk4root_cpu(consts, x0, u, z0, par, ts, n_fe, n_steps=1, max_newton=6, tol=1e-11):
+    """The rk4root plant (``MpcEvaluator.plant_rk4root``) on the host, no device: ``consts`` are the
+    model constants (``Kite3Constants`` or their vector), x0 [B, 11], u [B, n_steps, 6], z0 [B, 12],
+    par [B, 4] numpy arrays.  Returns dict(xf [B, n_steps, 11], zf [B, 12], qf [B, n_steps], res [B])."""
+    lib = load_library()
+    c = np.ascontiguousarray(getattr(consts, "consts", consts), dtype=np.float64)
+    x0 = np.ascontiguousarray(x0, dtype=np.float64)
+    B = x0.shape[0] if x0.ndim == 2 else 0
+    arrs = [x0] + [np.ascontiguousarray(a, dtype=np.float64) for a in (u, z0, par)]
+    if B >= 1 and n_steps >= 1:
+        for a, shape in zip(arrs, ((B, k3.NX), (B, n_steps, k3.NU), (B, PLANT_NUNK), (B, PLANT_NPAR))):
+            if a.shape != shape:
+                raise ValueError(f"expected an array of shape {shape}, got {a.shape}")
+    out = {"xf": np.zeros((max(B, 0), max(n_steps, 0), k3.NX)), "zf": np.zeros((max(B, 0), PLANT_NUNK)),
+           "qf": np.zeros((max(B, 0), max(n_steps, 0))), "res": np.zeros(max(B, 0))}
+    rc = lib.awempc_plant_rk4root_cpu(nb._dptr(c), c.size, B, *(nb._dptr(a) for a in arrs), float(ts), int(n_fe),
+                                      int(n_steps), int(max_newton), float(tol), *(nb._dptr(a) for a in out.values()))
+    if rc != nb.AWE_OK:
+        raise nb.AwegpuError(f"awempc error {rc}: {nb.last_error(lib, PREFIX)}")
+    return out
+
+
 class MpcEvaluator(nb.GeneratedPathMixin, nb.NlpEvaluator):
     """HIP evaluator of the 3-DOF tracking-MPC NLP for ``batch`` (V, p) instances.
     ``eval_nlp_device`` runs the dual-number kernel on contiguous grad_f / jac and the generated node
@@ -61,3 +92,31 @@ class MpcEvaluator(nb.GeneratedPathMixin, nb.NlpEvaluator):
     @staticmethod
     def _layout(consts):
         return k3.MpcLayout(consts.cfg.n_k, consts.cfg.d)
+
+    def plant_rk4root(self, x0, u, z0, par, ts, n_fe, n_steps=1, max_newton=6, tol=1e-11, stream=None):
+        """The reference's simulation plant (sim.py:72-78 -> rk4root) for all ``batch`` loops in one
+        launch: ``n_steps`` sampling times of length ``ts`` [s], ``n_fe`` RK4 steps each, the control
+        u[:, s] held over sampling time s, a Newton rootfinder for (xdot, z) at every stage and at the end
+        of every sampling time.  Contiguous float64 CUDA tensors x0 [B, 11], u [B, n_steps, 6] (scaled),
+        z0 [B, 12] (rootfinder guess: xdot, lambda), par [B, 4] (theta.diam_t, theta.t_f, phi.gamma,
+        u_ref).  Returns (xf [B, n_steps, 11], zf [B, 12] at the last xf, qf [B, n_steps] power integral
+        of each sampling time, res [B] largest rootfinder residual)."""
+        import torch
+        B = self.batch
+        for t, shape in ((x0, (B, k3.NX)), (u, (B, max(n_steps, 0), k3.NU)), (z0, (B, PLANT_NUNK)),
+                         (par, (B, PLANT_NPAR))):
+            if t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != shape:
+                raise ValueError(f"expected a contiguous float64 CUDA tensor of shape {shape}")
+        f64 = dict(dtype=torch.float64, device=x0.device)
+        xf, zf = torch.empty(B, max(n_steps, 0), k3.NX, **f64), torch.empty(B, PLANT_NUNK, **f64)
+        qf, res = torch.empty(B, max(n_steps, 0), **f64), torch.empty(B, **f64)
+        self._call("plant_rk4root", x0.data_ptr(), u.data_ptr(), z0.data_ptr(), par.data_ptr(), float(ts), int(n_fe),
+                   int(n_steps), int(max_newton), float(tol), xf.data_ptr(), zf.data_ptr(), qf.data_ptr(),
+                   res.data_ptr(), self._stream(stream))
+        return xf, zf, qf, res
+
+    def last_plant_ms(self):
+        """HIP-event time of the last ``plant_rk4root`` kernel, ms."""
+        a, = nb._floats(1)
+        self._call("last_plant_ms", ctypes.byref(a))
+        return a.value

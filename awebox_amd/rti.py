@@ -16,7 +16,8 @@ step per sampling time for every loop, all loops batched:
   continuity and initial-condition multipliers (462 unknowns, B blocks, same kernel);
 * plant: the first sampling interval is integrated with the applied control by the model's own
   radau collocation (Newton on the shooting and collocation rows of interval 0, the interval's
-  60 x 60 block of J_g) -- the collocation integrator of ``sim``;
+  60 x 60 block of J_g) -- the collocation integrator of ``sim``; or by ``sim``'s default rk4root,
+  as a host loop around the evaluator or fused into one kernel launch (``plant=``);
 * shift: the horizon moves one interval (the new last interval copies the old one).
 
 The path inequalities (tether stress, acceleration) and variable bounds are not part of the
@@ -69,7 +70,8 @@ class BatchedRti:
         eval_nlp_device); default = the HIP evaluator (awempc) for ``batch`` instances.
         ``plant``: "collocation" (interval 0's Radau collocation) or "rk4root" (the reference's
         sim integrator: ``n_fe`` RK4 steps per sampling time, the algebraic and derivative
-        variables by a Newton rootfinder at every stage; tools/integrator_routines.py:32-96).
+        variables by a Newton rootfinder at every stage; tools/integrator_routines.py:32-96), or
+        "rk4root_fused": the same integrator in one kernel launch (awempc_plant_rk4root).
         ``fix_fict``: the fictitious forces stay at 0 (pmpc.py:181-190); False frees them."""
         self.consts, self.B, self.dev = consts, batch, torch.device(device)
         cfg = consts.cfg
@@ -225,8 +227,10 @@ class BatchedRti:
         self.pl_keep = t(np.array(pk))
         self.pl_dst = t(np.array([rsel[int(jr_all[e])] * n_pl + csel[int(jc_all[e])] for e in pk]))
         self.x_idx = [t(lay.x(0))] + [t(lay.coll_x(0, j)) for j in range(cfg.d)]
-        if plant not in ("collocation", "rk4root"):
+        if plant not in ("collocation", "rk4root", "rk4root_fused"):
             raise ValueError(f"unknown plant {plant!r}")
+        if plant == "rk4root_fused" and not hasattr(self.ev, "plant_rk4root"):
+            raise ValueError("plant='rk4root_fused' needs the HIP evaluator (MpcEvaluator.plant_rk4root)")
         self.plant, self.n_fe = plant, n_fe
         self.plant_tol = 1e-9                   # step(): plant_converged = residual <= plant_tol
         self.sim_blocks = self.sim_xs = None
@@ -481,7 +485,8 @@ class BatchedRti:
         horizon shifted.  Returns per-loop diagnostics."""
         kkt_res, path_max = self.iterate()
         self.u0 = self.V[:, self.u0_idx].clone()
-        x1, plant_res = self._plant() if self.plant == "collocation" else self._rk4root()
+        x1, plant_res = {"collocation": self._plant, "rk4root": self._rk4root,
+                         "rk4root_fused": self._rk4root_fused}[self.plant]()
         self._shift(x1)
         self.step_count += 1
         x_ref = self.P[:, self.lay.p_ref + self.lay.x(0)[0]:self.lay.p_ref + self.lay.x(0)[0] + k3.NX]
@@ -546,6 +551,43 @@ class BatchedRti:
             k4 = ode(x + h * k3_)
             x = x + h * (k1 + 2.0 * k2 + 2.0 * k3_ + k4) / 6.0
         return x, worst
+
+    def _plant_inputs(self):
+        """What ``_rk4root`` reads, as the fused kernel takes it: x0 from P; the rootfinder guess
+        (xdot[0], z[0]) and par = (theta, phi.gamma, u_ref) from V and P."""
+        lay = self.lay
+        x0 = self.P[:, lay.p_x0:lay.p_x0 + k3.NX].contiguous()
+        z0 = self.V[:, self.rk_cols].contiguous()
+        par = torch.cat([self.V[:, :k3.NTH + 1], self.P[:, lay.p_u_ref:lay.p_u_ref + 1]], dim=1).contiguous()
+        return x0, z0, par
+
+    def _rk4root_fused(self, max_newton=6, tol=1e-11):
+        """``_rk4root`` in one kernel launch (MpcEvaluator.plant_rk4root, one lane per loop): the same
+        integrator from the same x0, applied u[0], rootfinder guess and parameters.  Returns (x1, the
+        largest rootfinder residual); ``plant_z`` and ``plant_q`` keep (xdot, z) at x1 and the
+        sampling time's power integral."""
+        x0, z0, par = self._plant_inputs()
+        u = self.V[:, self.u0_idx].reshape(self.B, 1, k3.NU).contiguous()
+        xf, self.plant_z, qf, res = self.ev.plant_rk4root(x0, u, z0, par, self.consts.cfg.ts, self.n_fe, 1,
+                                                          max_newton, tol)
+        self.plant_q = qf[:, 0]
+        return xf[:, 0], res
+
+    def simulate_open_loop(self, u_seq, max_newton=6, tol=1e-11):
+        """Open-loop simulation of every loop's plant (sim.py's ``open_loop`` run(n_sim, x0, u_sim)) in
+        one kernel launch: from the current x0 with the scaled controls ``u_seq`` [B, n_sim, 6], one per
+        sampling time (zero-order hold).  The loops' state is left as it is.  Returns dict(x [B, n_sim,
+        11] the state after every sampling time, q [B, n_sim] the power integral of each [J], z [B, 12]
+        (xdot, z) at the last state, residual [B])."""
+        if not hasattr(self.ev, "plant_rk4root"):
+            raise ValueError("simulate_open_loop needs the HIP evaluator (MpcEvaluator.plant_rk4root)")
+        if u_seq.ndim != 3 or u_seq.shape[0] != self.B or u_seq.shape[2] != k3.NU or u_seq.shape[1] < 1:
+            raise ValueError(f"u_seq must be [{self.B}, n_sim >= 1, {k3.NU}]")
+        x0, z0, par = self._plant_inputs()
+        u = u_seq.to(dtype=torch.float64, device=self.dev).contiguous()
+        xf, zf, qf, res = self.ev.plant_rk4root(x0, u, z0, par, self.consts.cfg.ts, self.n_fe, u.shape[1],
+                                                max_newton, tol)
+        return {"x": xf, "q": qf, "z": zf, "residual": res}
 
     def _shift(self, x1):
         """Move the horizon one interval: V[k] <- V[k+1], keep the last interval; new x0 and the

@@ -109,6 +109,25 @@ int awempc_eval_nlp_im(awempc_handle h, const double* V, const double* p, double
 /* kernel times of the last awempc_eval_nlp_im: input transposition, node kernel, finalize (ms) */
 int awempc_last_kernel_ms_im(awempc_handle h, float* ms_in, float* ms_node, float* ms_finalize);
 
+/* ---- the simulation plant ---------------------------------------------------------------------
+ * sim.py's plant (sim.py:72-78): rk4root over n_steps sampling times of length ts [s], n_fe RK4 steps
+ * each, the control of a sampling time held over it; at every stage, and at the end of every sampling
+ * time, a Newton rootfinder solves the shooting node's 12 equalities for (xdot, z) (at most max_newton
+ * solves, until max |row| < tol), warm-started from the previous one.  One launch, one lane per loop.
+ * x0[B][11], u[B][n_steps][6] (scaled), z0[B][12] = rootfinder guess (xdot(11), lambda), par[B][4] =
+ * theta.diam_t, theta.t_f, phi.gamma (scaled), u_ref.  Out: xf[B][n_steps][11], zf[B][12] at the last
+ * xf, qf[B][n_steps] = the power integral of each sampling time [J], res[B] = the largest rootfinder
+ * residual at exit.  B = the handle's batch.  Device pointers, asynchronous on `stream`. */
+int awempc_plant_rk4root(awempc_handle h, const double* x0, const double* u, const double* z0, const double* par,
+                         double ts, int n_fe, int n_steps, int max_newton, double tol, double* xf, double* zf,
+                         double* qf, double* res, void* stream);
+/* the same core on the host, no device and no handle (as the *_static sparsity calls): host pointers */
+int awempc_plant_rk4root_cpu(const double* consts, int n_consts, int batch, const double* x0, const double* u,
+                             const double* z0, const double* par, double ts, int n_fe, int n_steps, int max_newton,
+                             double tol, double* xf, double* zf, double* qf, double* res);
+/* kernel time of the last awempc_plant_rk4root (HIP events on its stream), ms */
+int awempc_last_plant_ms(awempc_handle h, float* ms);
+
 /* ---- nlp_hess_l ----------------------------------------------------------------------------------
  * Hessian of sigma f + lam^T g w.r.t. V, upper triangle (row <= col), CCS over the n_v columns:
  * H[b*nnz_h + i].  sigma[b], lam[b*n_g + i].  The structure is derived on the host from the node

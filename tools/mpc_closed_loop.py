@@ -19,7 +19,7 @@ def main():
     ap.add_argument("--n-k", type=int, default=20)
     ap.add_argument("--d", type=int, default=4)
     ap.add_argument("--out", default=None)
-    ap.add_argument("--plant", choices=["collocation", "rk4root"], default="collocation")
+    ap.add_argument("--plant", choices=["collocation", "rk4root", "rk4root_fused"], default="collocation")
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -40,7 +40,7 @@ def main():
         r.u0 = r.V[:, r.u0_idx].clone()
         sync()
         t1 = time.perf_counter()
-        x1, pres = r._plant() if a.plant == "collocation" else r._rk4root()
+        x1, pres = {"collocation": r._plant, "rk4root": r._rk4root, "rk4root_fused": r._rk4root_fused}[a.plant]()
         sync()
         t2 = time.perf_counter()
         r._shift(x1)
