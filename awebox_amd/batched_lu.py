@@ -79,6 +79,19 @@ def lu_solve(LU, piv, B):
     return X[0] if squeeze else X
 
 
+def factor(A):
+    """Batched LU wherever A lives: lu_factor for device tensors, LAPACK (torch.linalg.lu_factor) for
+    host tensors -- the CPU test harness, which never loads the library."""
+    import torch
+    return lu_factor(A) if A.is_cuda else torch.linalg.lu_factor(A)
+
+
+def solve(LU, piv, X):
+    """A^-1 X from factor's (LU, piv): lu_solve on the device, torch.linalg.lu_solve on the host."""
+    import torch
+    return lu_solve(LU, piv, X) if LU.is_cuda else torch.linalg.lu_solve(LU, piv, X)
+
+
 def btd_factor(T):
     """Factor block-tridiagonal systems T [batch, nb, 3, m, m] (sub-, main, super-diagonal block of
     every block row; float64 CUDA, m <= 48).  Returns (F, Dinv): F = T with W_k in the super-diagonal

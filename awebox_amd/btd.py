@@ -1,8 +1,9 @@
 """Bordered block-tridiagonal separator systems of the structured KKT solve.
 
-After the interval interiors are eliminated (ipm.StructuredKKT, rti.BatchedRti), the separators
-are the shooting states x[k], the multipliers c[k] of the continuity rows and a few global
-unknowns (free globals such as t_f, the multipliers of the periodicity and global rows).  In
+After the interval interiors are eliminated (ipm.StructuredKKT; rti.BatchedRti has no border and
+assembles its own chain for the fused kernels), the separators are the shooting states x[k], the
+multipliers c[k] of the continuity rows and a few global unknowns (free globals such as t_f, the
+multipliers of the periodicity and global rows).  In
 stages [c[k-1], x[k]] the separator matrix is block tridiagonal -- interval k's Schur complement
 touches only (x[k], c[k]) and the globals, the continuity row k couples c[k] with x[k+1] -- apart
 from the globals, which form a border:
@@ -25,7 +26,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import det
+from . import batched_lu, det
 
 
 class BorderedBtd:
@@ -113,7 +114,7 @@ class BorderedBtd:
                 self.Z = self._t_backward(Yf)
             Cp = C.view(B, nG, nG) - det.bmm(self.Fm, self.Z)
             self.Cp = Cp
-            self.Cf = self._lu(Cp)
+            self.Cf = batched_lu.factor(Cp)
 
     def inertia(self):
         """[B, 3] (positive, negative, zero) eigenvalue counts of the separator matrix S: the pivot
@@ -165,7 +166,7 @@ class BorderedBtd:
                     P = det.bmm(T[:, k, 0], torch.cat([Ws[k - 1], Y[k - 1]], 2))
                     D = T[:, k, 1] - P[:, :, :m]
                     rk = X[:, k] - P[:, :, m:]
-            LU = self._lu(D.contiguous())
+            LU = batched_lu.factor(D.contiguous())
             Dp.append(D)
             LUs.append(LU)
             if k < nb - 1:
@@ -199,10 +200,9 @@ class BorderedBtd:
         choice follows the batch count).  Round 5 measured the library getrs ahead for the dual
         kites' 100 x 100 blocks (the dual homotopy's first 62 iterations 3.8 s against 4.3 s,
         profiles/r05/solver/dual_solve_ab); batch invariance decides.  Host tensors: LAPACK."""
-        if X.is_cuda and self.AWELU_SOLVE:
-            from .batched_lu import lu_solve
-            return lu_solve(LU[0], LU[1], X)
-        return torch.linalg.lu_solve(LU[0], LU[1], X)
+        if not self.AWELU_SOLVE:
+            return torch.linalg.lu_solve(LU[0], LU[1], X)
+        return batched_lu.solve(LU[0], LU[1], X)
 
     def _t_solve(self, X):
         B, nb, m = self.B, self.nb, self.m
@@ -220,19 +220,6 @@ class BorderedBtd:
             Y[k] = Y[k] - det.bmm(self.Ws[k], Y[k + 1])
         return torch.stack(Y, 1).reshape(B, nb * m, -1)
 
-    @staticmethod
-    def _lu(A):
-        if A.is_cuda:
-            from .batched_lu import lu_factor
-            return lu_factor(A)
-        return torch.linalg.lu_factor(A)
-
-    def _c_solve(self, X):
-        if X.is_cuda:
-            from .batched_lu import lu_solve
-            return lu_solve(*self.Cf, X)
-        return torch.linalg.lu_solve(*self.Cf, X)
-
     def solve(self, r):
         """r [n_S] (or [B, n_S]) -> S^-1 r."""
         r2 = r.unsqueeze(0) if r.dim() == 1 else r
@@ -243,7 +230,7 @@ class BorderedBtd:
         x = torch.empty_like(r2)
         if self.nG:
             rG = r2[:, self.sep_g] - det.bmv(self.Fm, z)
-            xG = self._c_solve(rG.unsqueeze(-1)).squeeze(-1)
+            xG = batched_lu.solve(*self.Cf, rG.unsqueeze(-1)).squeeze(-1)
             z = z - det.bmv(self.Z, xG)
             x[:, self.sep_g] = xG
         x[:, self.sep_t] = z[:, self.slot_t]

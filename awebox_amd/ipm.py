@@ -41,7 +41,8 @@ from dataclasses import dataclass, field
 import numpy as np
 import torch
 
-from . import det
+from . import batched_lu, det
+from . import kkt_partition as kp
 from .ipm_measures import Measures
 from .nlp_binding import solver_tensors
 from . import problem as pb
@@ -482,36 +483,12 @@ class StructuredKKT:
         self.N, self.dev, self.ny = N, dev, ny
         n_k, stride, v0, rows = lay.n_k, lay.interval_stride, lay.v_intervals, lay.rows_per_interval
         nx = getattr(lay, "nx", pb.NX)                          # states per shooting node
-        owner = np.full(N, -1, dtype=np.int64)                  # interval of an interior unknown
+        g0 = getattr(lay, "g_int0", 0)                          # the MPC NLP leads with nx initial-condition rows
         free = np.asarray(nlp.free.cpu().numpy() if torch.is_tensor(nlp.free) else nlp.free, dtype=np.int64)
-        kf, of = np.divmod(free - v0, stride)
-        inner = (free >= v0) & (kf < n_k) & (of >= nx)
-        owner[:n][inner] = kf[inner]
-        # interval rows start at g0: the MPC NLP leads with nx initial-condition rows
-        # (ocp/operation.py:303-326), the periodic NLP has none
-        g0 = getattr(lay, "g_int0", 0)
-        if g0 > nx:
-            raise ValueError("more leading rows than states per node")
-        rr_ = np.asarray(nlp.ineq, dtype=np.int64) - g0
-        # global rows (t_f bounds): separators
-        owner[n:n + len(rr_)] = np.where((rr_ >= 0) & (rr_ < n_k * rows), rr_ // rows, -1)
-        # interval rows, except the continuity rows: an interval has more rows than interior
-        # unknowns (x[k], x[k+1] close the count), so their multipliers join the separators
-        rr = np.arange(m) - g0
-        owner[ny + np.arange(m)] = np.where((rr >= 0) & (rr < n_k * rows) & (rr % rows < rows - nx), rr // rows, -1)
-        self.owner = owner
-        sep = np.where(owner < 0)[0]
-        self.nS = len(sep)
-        sep_id = np.full(N, -1, dtype=np.int64)
-        sep_id[sep] = np.arange(self.nS)
-        loc = np.full(N, -1, dtype=np.int64)                    # position within the interval's block
-        ip = np.where(owner >= 0)[0]
-        counts = np.bincount(owner[ip], minlength=n_k).astype(np.int64)
-        by_k = np.argsort(owner[ip], kind="stable")
-        first = np.concatenate([[0], np.cumsum(counts)[:-1]])
-        loc[ip[by_k]] = np.arange(len(ip)) - first[owner[ip][by_k]]
-        self.nI = int(counts.max())
-        self.n_k = n_k
+        # interval of an interior unknown: free columns, slacks (with their rows), multipliers
+        owner = np.concatenate([kp.column_owner(free, lay), kp.row_owner(nlp.ineq, lay),
+                                kp.row_owner(np.arange(m), lay)])
+        self.owner, self.n_k = owner, n_k
         # KKT pattern in COO (both orientations), in the order of the value vector of factor()
         hr, hc = nlp.h_r.cpu().numpy(), nlp.h_c.cpu().numpy()
         off = hr != hc
@@ -524,35 +501,18 @@ class StructuredKKT:
         self.P_, self.Q_ = torch.tensor(P_, device=dev), torch.tensor(Q_, device=dev)
         self.Q32 = self.Q_.to(torch.int32)
         self.n_solve = self.n_dense = 0
-        oP, oQ = owner[P_], owner[Q_]
-        ii = (oP >= 0) & (oP == oQ)
-        is_ = (oP >= 0) & (oQ < 0)
-        ss = (oP < 0) & (oQ < 0)
-        if ((oP >= 0) & (oQ >= 0) & (oP != oQ)).any():
-            raise ValueError("KKT couples the interiors of two intervals")
-        lsep = [sorted(set(sep_id[Q_[is_ & (oP == k)]].tolist())) for k in range(n_k)]
-        self.L = max(1, max(len(l) for l in lsep))
-        lsep_arr = np.full((n_k, self.L), self.nS, dtype=np.int64)      # padding -> dummy separator
-        lpos = np.full((n_k, self.nS + 1), -1, dtype=np.int64)
-        for k, l in enumerate(lsep):
-            lsep_arr[k, :len(l)] = l
-            lpos[k, l] = np.arange(len(l))
+        part = kp.IntervalPartition(owner, P_, Q_, n_k)
+        self.nI, self.nS, self.L = part.nI, part.nS, part.L
+        nS, sep, lsep_arr = part.nS, part.sep, part.lsep_arr
         self.lsep = torch.tensor(lsep_arr, device=dev)
-        nI, L, nS = self.nI, self.L, self.nS
-        self.sel_ii = torch.tensor(np.where(ii)[0], device=dev)
-        dst_ii = oP[ii] * nI * nI + loc[P_[ii]] * nI + loc[Q_[ii]]
-        isi = np.where(is_)[0]
-        self.sel_is = torch.tensor(isi, device=dev)
-        dst_is = oP[isi] * nI * L + loc[P_[isi]] * L + lpos[oP[isi], sep_id[Q_[isi]]]
-        self.sel_ss = torch.tensor(np.where(ss)[0], device=dev)
-        dst_ss = sep_id[P_[ss]] * (nS + 1) + sep_id[Q_[ss]]
-        pk, pj = np.nonzero(np.arange(nI)[None, :] >= counts[:, None])   # padding rows, by interval
-        self.n_pad = len(pk)
-        self.pad_flat = torch.tensor(pk * nI * nI + pj * nI + pj, dtype=torch.int64, device=dev)
-        schur_flat = (lsep_arr[:, :, None] * (nS + 1) + lsep_arr[:, None, :]).reshape(-1)
-        int_p = np.where(owner >= 0)[0]
-        self.int_p = torch.tensor(int_p, device=dev)
-        self.sc = [scatter_sum(t, dev) for t in (dst_ii, dst_is, dst_ss, schur_flat)]
+        self.sel_ii, self.sel_is, self.sel_ss = (torch.tensor(a, device=dev) for a in (part.ii, part.is_, part.ss))
+        self.n_pad = len(part.pad)
+        self.pad_flat = torch.tensor(part.pad, dtype=torch.int64, device=dev)
+        self.int_p, self.int_flat, self.sep_p = (torch.tensor(a, device=dev)
+                                                 for a in (part.int_p, part.int_flat, part.sep_p))
+        dst_ss = part.ss_r * (nS + 1) + part.ss_c
+        schur_flat = (part.r_idx * (nS + 1) + part.c_idx).reshape(-1)
+        self.sc = [scatter_sum(t, dev) for t in (part.dst_ii, part.dst_is, dst_ss, schur_flat)]
         self.sc_mv = scatter_sum(P_, dev)
         self.sc_dense = scatter_sum(P_ * N + Q_, dev)
         self.sc_rs = scatter_sum(lsep_arr.reshape(-1), dev)
@@ -583,17 +543,13 @@ class StructuredKKT:
             stage_of[qc[ic]], pos_of[qc[ic]] = 0, rq[ic] + g0
             ct = (rq >= 0) & (rq < n_k * rows) & (rq % rows >= rows - nx)
             stage_of[qc[ct]], pos_of[qc[ct]] = rq[ct] // rows + 1, rq[ct] % rows - (rows - nx)
-            ss_r, ss_c = sep_id[P_[ss]], sep_id[Q_[ss]]
-            sch_r, sch_c = lsep_arr[:, :, None].repeat(L, 2), lsep_arr[:, None, :].repeat(L, 1)
             from .btd import BorderedBtd
             try:
                 self.btd = BorderedBtd(stage_of, pos_of, n_k + 1, 2 * nx,
-                                       np.concatenate([ss_r, sch_r.reshape(-1)]),
-                                       np.concatenate([ss_c, sch_c.reshape(-1)]), dev)
+                                       np.concatenate([part.ss_r, part.r_idx.reshape(-1)]),
+                                       np.concatenate([part.ss_c, part.c_idx.reshape(-1)]), dev)
             except ValueError:
                 self.btd = None                                 # not stage-structured: dense S
-        self.int_flat = torch.tensor(owner[int_p] * nI + loc[int_p], device=dev)
-        self.sep_p = torch.tensor(sep, device=dev)
         self._cI = None                                         # interval-block counts in flight (factor)
 
     # ---------------------------------------------------------------------------------------
@@ -626,12 +582,8 @@ class StructuredKKT:
         if early_inertia and KII.is_cuda and B * n_k <= EARLY_INERTIA_MAX_BLOCKS:
             self._interval_inertia_async(KII)
         KIS = self.sc[1].add_into_sel(torch.zeros(B, n_k * nI * L, **f64), vals, self.sel_is).view(B * n_k, nI, L)
-        self.awelu = self.lu_backend == "awelu" and KII.is_cuda   # the CPU test harness uses LAPACK
-        if self.awelu:
-            from .batched_lu import lu_factor
-            self.LU_I, self.piv_I = lu_factor(KII)
-        else:
-            self.LU_I, self.piv_I = torch.linalg.lu_factor(KII)
+        lu = torch.linalg.lu_factor if self.lu_backend == "torch" else batched_lu.factor
+        self.LU_I, self.piv_I = lu(KII)
         self.X = self._block_solve(KIS)                                        # K_II^-1 K_IS
         T = det.bmm(KIS.transpose(1, 2), self.X).reshape(B, n_k * L * L)       # [B, n_k L L]
         self.KIS = KIS
@@ -759,10 +711,9 @@ class StructuredKKT:
         """K_II^-1 B for all interval blocks: the awelu solve kernel (right-hand sides resident in
         LDS; rocBLAS's batched trsv took 2.4 ms per one-column solve of 320 blocks) on the device,
         LAPACK in the CPU harness."""
-        if self.awelu:
-            from .batched_lu import lu_solve
-            return lu_solve(self.LU_I, self.piv_I, B)
-        return torch.linalg.lu_solve(self.LU_I, self.piv_I, B)
+        if self.lu_backend == "torch":
+            return torch.linalg.lu_solve(self.LU_I, self.piv_I, B)
+        return batched_lu.solve(self.LU_I, self.piv_I, B)
 
     def _solve(self, rhs):
         if rhs.dim() == 1:
@@ -817,13 +768,6 @@ def cached_kkt_structures():
     return [e[0] for e in _STRUCT_CACHE.values()]
 
 
-def _layout_key(lay):
-    """What StructuredKKT reads from a layout: two evaluators whose layouts agree here (and whose NLPs
-    have the same patterns) share one structure."""
-    return (type(lay).__name__, lay.n_k, lay.interval_stride, lay.v_intervals, lay.rows_per_interval,
-            getattr(lay, "nx", pb.NX), getattr(lay, "g_int0", 0))
-
-
 def _structure(ev, nlp, dev, opts):
     """(StructuredKKT, J^T product, H product) for one NLP structure, shared by the solves with the
     same layout and the same fixed-variable / inequality sets and patterns, whichever evaluator (and
@@ -838,7 +782,7 @@ def _structure(ev, nlp, dev, opts):
               nlp.h_c.cpu().numpy()):
         h.update(np.ascontiguousarray(a, dtype=np.int64).tobytes())
         h.update(b"|")
-    key = (_layout_key(ev.layout), len(nlp.x_fix), h.hexdigest(),
+    key = (kp.layout_key(ev.layout), len(nlp.x_fix), h.hexdigest(),
            str(torch.device(dev)), opts.lu_backend, opts.separators)
     ent = _STRUCT_CACHE.get(key)
     if ent is not None:

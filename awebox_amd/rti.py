@@ -34,9 +34,11 @@ import time
 import numpy as np
 import torch
 
+from . import batched_lu
 from . import kite3 as k3
 from .collocation import coefficients
 from .ipm import scatter_sum
+from .kkt_partition import IntervalPartition, block_entries, column_owner, group_positions, row_owner
 from .nlp_binding import solver_tensors
 
 
@@ -98,31 +100,6 @@ class BatchedRti:
         colmap[self.free] = np.arange(nw)
         rowmap = -np.ones(n_g, dtype=np.int64)
         rowmap[self.eq] = np.arange(ne)
-        # owner interval of every unknown (-1 = separator)
-        owner = np.full(self.N, -1, dtype=np.int64)
-        for p, v in enumerate(self.free):
-            k, o = divmod(v - v0, st)
-            if k < nk and o >= nx:
-                owner[p] = k
-        rows_pi = lay.rows_per_interval
-        for i, r in enumerate(self.eq):
-            if r >= nx:
-                k, o = divmod(r - nx, rows_pi)
-                if o < rows_pi - nx:                 # node / collocation rows; continuity -> separator
-                    owner[nw + i] = k
-        sep = np.where(owner < 0)[0]
-        nS = len(sep)
-        sep_id = np.full(self.N, -1, dtype=np.int64)
-        sep_id[sep] = np.arange(nS)
-        loc = np.full(self.N, -1, dtype=np.int64)
-        counts = np.zeros(nk, dtype=np.int64)
-        for p in np.where(owner >= 0)[0]:
-            loc[p] = counts[owner[p]]
-            counts[owner[p]] += 1
-        nI = int(counts.max())
-        if counts.min() != nI:
-            raise ValueError("unequal interval interiors")
-        self.nI, self.nS, self.nk = nI, nS, nk
         # ---- KKT pattern (both orientations): H diagonal, J (eq rows, free cols), -dc I
         colind, row = self.ev.sparsity_jac()
         jcol = np.repeat(np.arange(n_v), np.diff(colind))
@@ -134,45 +111,26 @@ class BatchedRti:
         Q_ = np.concatenate([np.arange(nw), jc, jr, nw + np.arange(ne)])
         self.nh = nw
         self.nj = len(jr)
-        oP, oQ = owner[P_], owner[Q_]
-        if ((oP >= 0) & (oQ >= 0) & (oP != oQ)).any():
-            raise ValueError("KKT couples two interval interiors")
-        ii, is_, ss = (oP >= 0) & (oP == oQ), (oP >= 0) & (oQ < 0), (oP < 0) & (oQ < 0)
-        lsep = [sorted(set(sep_id[Q_[is_ & (oP == k)]].tolist())) for k in range(nk)]
-        L = max(len(x) for x in lsep)
-        lsep_arr = np.full((nk, L), nS, dtype=np.int64)
-        lpos = np.full((nk, nS + 1), -1, dtype=np.int64)
-        for k, l_ in enumerate(lsep):
-            lsep_arr[k, :len(l_)] = l_
-            lpos[k, l_] = np.arange(len(l_))
-        self.L = L
+        # interiors and separators (kkt_partition): the owner interval of every unknown, -1 = separator
+        part = IntervalPartition(np.concatenate([column_owner(self.free, lay), row_owner(self.eq, lay)]), P_, Q_, nk)
+        if part.counts.min() != part.nI:
+            raise ValueError("unequal interval interiors")
+        nI, nS, L, sep, r_idx, c_idx = part.nI, part.nS, part.L, part.sep, part.r_idx, part.c_idx
+        self.nI, self.nS, self.nk, self.L = nI, nS, nk, L
         t = lambda a: torch.tensor(a, device=self.dev)  # noqa: E731
         bI, bIS = nk * nI * nI, nk * nI * L
         bo = np.arange(B)[:, None]
-        self.sel_ii, self.sel_is, self.sel_ss = t(np.where(ii)[0]), t(np.where(is_)[0]), t(np.where(ss)[0])
-        self.dst_ii = t((oP[ii] * nI * nI + loc[P_[ii]] * nI + loc[Q_[ii]])[None, :] + bo * bI).reshape(-1)
-        isi = np.where(is_)[0]
-        self.dst_is = t((oP[isi] * nI * L + loc[P_[isi]] * L + lpos[oP[isi], sep_id[Q_[isi]]])[None, :]
-                        + bo * bIS).reshape(-1)
-        r_idx = lsep_arr[:, :, None].repeat(L, axis=2)
-        c_idx = lsep_arr[:, None, :].repeat(L, axis=1)
-        self.lsep = t(lsep_arr)
+        self.sel_ii, self.sel_is, self.sel_ss = t(part.ii), t(part.is_), t(part.ss)
+        self.dst_ii = t(part.dst_ii[None, :] + bo * bI).reshape(-1)
+        self.dst_is = t(part.dst_is[None, :] + bo * bIS).reshape(-1)
+        self.lsep = t(part.lsep_arr)
         # ---- separators in stage order: stage 0 = [initial-condition multipliers, x[0]], stage
         # k + 1 = [continuity multipliers of interval k, x[k + 1]]; the separator system is then
         # block tridiagonal (awelu_btd_solve_batched).
-        stage = np.full(nS, -1, dtype=np.int64)
-        for q, p in enumerate(sep):
-            if p < nw:
-                stage[q] = (self.free[p] - v0) // st
-            else:
-                r = self.eq[p - nw]
-                stage[q] = 0 if r < nx else (r - nx) // rows_pi + 1
+        sx, sr = self.free[sep[sep < nw]], self.eq[sep[sep >= nw] - nw]     # separator columns and rows
+        stage = np.concatenate([(sx - v0) // st, np.where(sr < nx, 0, (sr - nx) // lay.rows_per_interval + 1)])
         nb = int(stage.max()) + 1
-        spos = np.zeros(nS, dtype=np.int64)
-        sizes = np.zeros(nb, dtype=np.int64)
-        for q in range(nS):
-            spos[q] = sizes[stage[q]]
-            sizes[stage[q]] += 1
+        spos, sizes = group_positions(stage, nb)                  # per stage: the states, then the multipliers
         m = int(sizes.max())
         self.nb, self.m = nb, m
 
@@ -183,7 +141,7 @@ class BatchedRti:
             return ((a * 3 + 1 + b_ - a) * m + spos[qr]) * m + spos[qc]
         bT = nb * 3 * m * m
         self.bT = bT
-        self.btd_ss = t(btd_index(sep_id[P_[ss]], sep_id[Q_[ss]])[None, :] + bo * bT).reshape(-1)
+        self.btd_ss = t(btd_index(part.ss_r, part.ss_c)[None, :] + bo * bT).reshape(-1)
         valid = (r_idx < nS) & (c_idx < nS)                      # [nk, L, L]
         self.schur_src = t(np.where(valid.reshape(-1))[0])
         self.btd_schur = t(btd_index(r_idx[valid], c_idx[valid])[None, :] + bo * bT).reshape(-1)
@@ -192,14 +150,11 @@ class BatchedRti:
         self._schur_sum = scatter_sum(self.btd_schur.cpu().numpy(), self.dev)
         self._rs_sum = scatter_sum(self.lsep.reshape(-1).cpu().numpy(), self.dev)
         T0 = np.zeros((nb, 3, m, m))
-        for a in range(nb):
-            for i in range(sizes[a], m):
-                T0[a, 1, i, i] = 1.0                              # padding of short stages
+        a_, i_ = np.nonzero(np.arange(m)[None, :] >= sizes[:, None])
+        T0[a_, 1, i_, i_] = 1.0                                   # padding of short stages
         self.T0 = t(T0.reshape(-1))
         self.sep_btd = t(stage * m + spos)                        # separator q -> stage-order slot
-        int_p = np.where(owner >= 0)[0]
-        self.int_p, self.int_flat = t(int_p), t(owner[int_p] * nI + loc[int_p])
-        self.sep_p = t(sep)
+        self.int_p, self.int_flat, self.sep_p = t(part.int_p), t(part.int_flat), t(sep)
         self.bI, self.bIS = bI, bIS
         self.delta_w, self.delta_c = delta_w, delta_c
         # ---- constant Gauss-Newton Hessian: the diagonal of the quadratic tracking cost
@@ -214,18 +169,14 @@ class BatchedRti:
         self.u0_idx = t(lay.u(0))
         self.hdiag = None
         # plant: interval 0's shooting + collocation rows against its interior unknowns
-        self.pl_rows = t(np.concatenate([lay.g_shooting(0), np.concatenate([lay.g_coll(0, j) for j in range(cfg.d)])]))
-        self.pl_cols = t(np.concatenate([lay.xdot(0), lay.z(0)] + [np.concatenate([lay.coll_x(0, j), lay.coll_z(0, j)])
-                                                                  for j in range(cfg.d)]))
-        jr_all, jc_all = row, jcol
-        rsel = {int(r): i for i, r in enumerate(self.pl_rows.cpu().numpy())}
-        csel = {int(c): i for i, c in enumerate(self.pl_cols.cpu().numpy())}
-        pk = [e for e in range(len(row)) if int(jr_all[e]) in rsel and int(jc_all[e]) in csel]
-        self.n_pl = n_pl = len(rsel)
-        if len(csel) != n_pl:
+        pl_rows = np.concatenate([lay.g_shooting(0)] + [lay.g_coll(0, j) for j in range(cfg.d)])
+        pl_cols = np.concatenate([lay.xdot(0), lay.z(0)] + [np.concatenate([lay.coll_x(0, j), lay.coll_z(0, j)])
+                                                            for j in range(cfg.d)])
+        self.n_pl = len(pl_rows)
+        if len(pl_cols) != self.n_pl:
             raise ValueError("interval 0 is not square in its interior unknowns")
-        self.pl_keep = t(np.array(pk))
-        self.pl_dst = t(np.array([rsel[int(jr_all[e])] * n_pl + csel[int(jc_all[e])] for e in pk]))
+        self.pl_rows, self.pl_cols = t(pl_rows), t(pl_cols)
+        self.pl_keep, self.pl_dst = map(t, block_entries(row, jcol, pl_rows, pl_cols))
         self.x_idx = [t(lay.x(0))] + [t(lay.coll_x(0, j)) for j in range(cfg.d)]
         if plant not in ("collocation", "rk4root", "rk4root_fused"):
             raise ValueError(f"unknown plant {plant!r}")
@@ -235,16 +186,12 @@ class BatchedRti:
         self.plant_tol = 1e-9                   # step(): plant_converged = residual <= plant_tol
         self.sim_blocks = self.sim_xs = None
         # rk4root: the shooting-node rows of interval 0 against (xdot[0], z[0])
-        self.rk_rows = t(lay.g_shooting(0))
-        self.rk_cols = t(np.concatenate([lay.xdot(0), lay.z(0)]))
-        rsel = {int(r): i for i, r in enumerate(lay.g_shooting(0))}
-        csel = {int(c): i for i, c in enumerate(np.concatenate([lay.xdot(0), lay.z(0)]))}
-        if len(rsel) != len(csel):
+        rk_rows, rk_cols = lay.g_shooting(0), np.concatenate([lay.xdot(0), lay.z(0)])
+        self.n_rk = len(rk_rows)
+        if len(rk_cols) != self.n_rk:
             raise ValueError("shooting rows and (xdot, z) do not form a square system")
-        pk = [e for e in range(len(row)) if int(jr_all[e]) in rsel and int(jc_all[e]) in csel]
-        self.n_rk = len(rsel)
-        self.rk_keep = t(np.array(pk))
-        self.rk_dst = t(np.array([rsel[int(jr_all[e])] * self.n_rk + csel[int(jc_all[e])] for e in pk]))
+        self.rk_rows, self.rk_cols = t(rk_rows), t(rk_cols)
+        self.rk_keep, self.rk_dst = map(t, block_entries(row, jcol, rk_rows, rk_cols))
         self.xdot_idx = t(lay.xdot(0))
         s_ = consts.scaling
         self.rk_ratio = torch.tensor(s_[k3.NX:2 * k3.NX] / s_[:k3.NX], dtype=torch.float64, device=self.dev)
@@ -409,28 +356,12 @@ class BatchedRti:
 
     # ------------------------------------------------------------------ one RTI ---------
     @staticmethod
-    def _lu(A):
-        """Batched LU: the awelu kernel for device blocks, torch's for host tensors (CPU tests)."""
-        if A.is_cuda:
-            from .batched_lu import lu_factor
-            return lu_factor(A)
-        return torch.linalg.lu_factor(A)
-
-    @staticmethod
-    def _solve(LU, piv, B):
-        if LU.is_cuda:
-            from .batched_lu import lu_solve
-            return lu_solve(LU, piv, B)
-        return torch.linalg.lu_solve(LU, piv, B)
-
-    @staticmethod
     def _btd(T, X):
-        from .batched_lu import btd_dense, btd_factor, btd_solve
         if T.is_cuda:
-            F, Dinv = btd_factor(T)
-            return btd_solve(F, Dinv, X)
+            F, Dinv = batched_lu.btd_factor(T)
+            return batched_lu.btd_solve(F, Dinv, X)
         b, nb, m, nrhs = X.shape
-        return torch.linalg.solve(btd_dense(T), X.reshape(b, nb * m, nrhs)).view(b, nb, m, nrhs)
+        return torch.linalg.solve(batched_lu.btd_dense(T), X.reshape(b, nb * m, nrhs)).view(b, nb, m, nrhs)
 
     def _factor_solve(self, rhs):
         B, nk, nI, L, nS = self.B, self.nk, self.nI, self.L, self.nS
@@ -445,11 +376,11 @@ class BatchedRti:
         Tb[self.btd_ss] = vals[:, self.sel_ss].reshape(-1)
         KII = KII.view(B * nk, nI, nI)
         KIS = KIS.view(B * nk, nI, L)
-        LU, piv = self._lu(KII)
+        LU, piv = batched_lu.factor(KII)
         rI = torch.zeros(B, nk * nI, **f64)
         rI[:, self.int_flat] = rhs[:, self.int_p]
         # K_II^-1 [K_IS | r_I] in one batched solve (the solve is latency-bound, not width-bound)
-        Xz = self._solve(LU, piv, torch.cat([KIS, rI.view(B * nk, nI, 1)], dim=2))
+        Xz = batched_lu.solve(LU, piv, torch.cat([KIS, rI.view(B * nk, nI, 1)], dim=2))
         X, z = Xz[:, :, :L], Xz[:, :, L:]
         Tsch = (KIS.transpose(1, 2) @ X).view(B, nk * L * L)
         self._schur_sum.add_into(Tb, -Tsch[:, self.schur_src].reshape(-1))
@@ -509,8 +440,8 @@ class BatchedRti:
                 break
             A = torch.zeros(self.B, n * n, dtype=torch.float64, device=self.dev)
             A[:, self.pl_dst] = self.jac[:, self.pl_keep]
-            LU, piv = self._lu(A.view(self.B, n, n))
-            Vp[:, self.pl_cols] -= self._solve(LU, piv, r.unsqueeze(-1).contiguous()).squeeze(-1)
+            LU, piv = batched_lu.factor(A.view(self.B, n, n))
+            Vp[:, self.pl_cols] -= batched_lu.solve(LU, piv, r.unsqueeze(-1).contiguous()).squeeze(-1)
         x1 = sum(float(self.D[r_]) * Vp[:, self.x_idx[r_]] for r_ in range(self.lay.d + 1))
         self.plant_V = Vp                       # interval 0's solved variables (simulated references)
         return x1, res
@@ -539,8 +470,8 @@ class BatchedRti:
                     break
                 A = torch.zeros(B, n * n, dtype=torch.float64, device=self.dev)
                 A[:, self.rk_dst] = self.jac[:, self.rk_keep]
-                LU, piv = self._lu(A.view(B, n, n))
-                Vp[:, self.rk_cols] -= self._solve(LU, piv, r.unsqueeze(-1).contiguous()).squeeze(-1)
+                LU, piv = batched_lu.factor(A.view(B, n, n))
+                Vp[:, self.rk_cols] -= batched_lu.solve(LU, piv, r.unsqueeze(-1).contiguous()).squeeze(-1)
             worst = torch.maximum(worst, res)
             return Vp[:, self.xdot_idx] * self.rk_ratio
 

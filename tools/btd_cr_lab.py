@@ -19,6 +19,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+from awebox_amd import batched_lu  # noqa: E402
 from awebox_amd.btd import BorderedBtd  # noqa: E402
 
 
@@ -54,7 +55,7 @@ class CrBtd(BorderedBtd):
             ke = torch.arange(0, n, 2, device=D.device)          # kept (even positions)
             ne = len(eo)
             De = D[:, eo].contiguous()
-            LUe = self._lu(De.reshape(B * ne, m, m))
+            LUe = batched_lu.factor(De.reshape(B * ne, m, m))
             GH = self._lu_solve(LUe, torch.cat([L[:, eo], U[:, eo]], 3).reshape(B * ne, m, 2 * m))
             GH = GH.view(B, ne, m, 2 * m)
             G, H = GH[..., :m], GH[..., m:]                       # D_e^-1 L_e, D_e^-1 U_e
@@ -75,7 +76,7 @@ class CrBtd(BorderedBtd):
             levels.append(dict(eo=eo, ke=ke, LUe=LUe, G=G, H=H, Lk=Lk, Uk=Uk, il=il, ir=ir, left=left, right=right))
             pivs.append(De)
             D, L, U = Dk, Ln, Un
-        LUf = self._lu(D[:, 0].contiguous())
+        LUf = batched_lu.factor(D[:, 0].contiguous())
         pivs.append(D)
         self.cr_levels, self.cr_last = levels, LUf
         self.cr_piv = torch.cat(pivs, 1)                          # [B, nb, m, m]

@@ -13,8 +13,8 @@ import json
 import os
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SOLVER_SOURCES = ["awebox_amd/ipm.py", "awebox_amd/btd.py", "awebox_amd/batched_lu.py", "awebox_amd/csrc/batched_lu.hip",
-                  "awebox_amd/sweep.py", "awebox_amd/trajectory.py", "awebox_amd/homotopy.py"]
+SOLVER_SOURCES = ["awebox_amd/ipm.py", "awebox_amd/kkt_partition.py", "awebox_amd/btd.py", "awebox_amd/batched_lu.py",
+                  "awebox_amd/csrc/batched_lu.hip", "awebox_amd/sweep.py", "awebox_amd/trajectory.py", "awebox_amd/homotopy.py"]
 EVAL_SOURCES = {"ap2": ["awebox_amd/csrc/awegpu.hip", "awebox_amd/csrc/ap2_model.hpp", "awebox_amd/csrc/ap2_tables.hpp"],
                 "dual": ["awebox_amd/csrc/awedual.hip", "awebox_amd/csrc/dual_model.hpp", "awebox_amd/csrc/dual_tables.hpp",
                          "awebox_amd/csrc/dual_hess_tables.hpp", "awebox_amd/dual_homotopy.py"]}
