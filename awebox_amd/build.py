@@ -63,7 +63,7 @@ TARGETS = {
     LIB: ([os.path.join(CSRC, "awegpu.hip")], _COMMON + [GEN_HEADER, HESS_HEADER]),
     LIB_MPC: ([os.path.join(CSRC, "awempc.hip")],
               _COMMON + [os.path.join(CSRC, f) for f in ("kite3_model.hpp", "kite3_tables.hpp",
-                                                         "plant_rk4root.hpp")]
+                                                         "plant_rk4root.hpp", "ref_pp.hpp")]
               + [os.path.join(INCLUDE, "awempc.h"), K3_HEADER, K3_ROOT_HEADER]),
     LIB_DUAL: ([os.path.join(CSRC, "awedual.hip"), os.path.join(CSRC, "awedual_gen.hip")],
                _COMMON + [os.path.join(CSRC, f) for f in ("dual_model.hpp", "dual_tables.hpp", "dual_hess_tables.hpp",

@@ -31,6 +31,7 @@
 #include "kite3_noderoot.gen.hpp"
 #include "kite3_tables.hpp"
 #include "plant_rk4root.hpp"
+#include "ref_pp.hpp"
 
 namespace {
 
@@ -949,6 +950,28 @@ __global__ __launch_bounds__(64) void mpc_plant_rk4root_kernel(PlantArgs a) {
     plant_instance(a, b, cs, sys);
 }
 
+// ---------------------------------------------------------------------------------------------
+// The MPC's reference generator (pmpc.py:408-550): ref_pp.hpp, one thread per (loop, time point).
+//   mpc_ref_window_kernel: the N + 1 shooting, N d collocation and N control points of a loop on
+//   consecutive threads; the three grids' breakpoints staged in LDS (the piece search reads them
+//   log2(pieces) times per point), the coefficients read piece-major from global memory (a point's
+//   channels are contiguous).  Every entry of the window is written here, the constant ones included.
+//   No cross-lane operation: a loop's window does not depend on the batch.
+//   awempc_ref_window_cpu runs the same core on the host.
+// ---------------------------------------------------------------------------------------------
+constexpr int kRefBlock = 256;
+
+__global__ __launch_bounds__(kRefBlock) void mpc_ref_window_kernel(awe::RefArgs a, const double* brk, int n_brk) {
+    __shared__ double sb[awe::kRefMaxBrk];
+    for (int i = threadIdx.x; i < n_brk && i < awe::kRefMaxBrk; i += kRefBlock) sb[i] = brk[i];
+    __syncthreads();
+    const int n_pt = awe::ref_points(a.n_k, a.d);
+    const size_t idx = (size_t)blockIdx.x * kRefBlock + threadIdx.x;
+    if (idx >= (size_t)a.batch * (size_t)n_pt) return;
+    const size_t b = idx / (size_t)n_pt;
+    awe::ref_point(a, sb, b, (int)(idx - b * (size_t)n_pt));
+}
+
 }  // namespace
 
 struct awempc_handle_s {
@@ -987,6 +1010,13 @@ struct awempc_handle_s {
     // rk4root plant (awempc_plant_rk4root)
     Event pev[2];
     bool ptimed = false;
+    // reference generator (awempc_ref_set, awempc_ref_window)
+    bool ref_ready = false;
+    awe::RefArgs ref{};                      // grids, period, offsets and head: device pointers
+    int ref_nbrk = 0;
+    DevBuf<double> d_ref_brk, d_ref_coef, d_ref_offs, d_ref_head;
+    Event rev[2];
+    bool rtimed = false;
 };
 
 namespace {
@@ -1085,6 +1115,7 @@ int awempc_create(int n_k, int d, const double* consts, int n_consts, int batch,
     HIP_TRY(h->d_fpart.alloc((size_t)batch * n_k));
     for (auto& e : h->ev) HIP_TRY(e.create());
     for (auto& e : h->pev) HIP_TRY(e.create());
+    for (auto& e : h->rev) HIP_TRY(e.create());
     if (int rc = build_gen(h.get())) return rc;
     *out = h.release();
     return AWE_OK;
@@ -1275,6 +1306,92 @@ int awempc_last_plant_ms(awempc_handle h, float* ms) {
     if (!h || !h->ptimed) return fail(AWE_ERR_ARG, "no timed plant call yet");
     HIP_TRY(hipEventSynchronize(h->pev[1]));
     if (ms) HIP_TRY(hipEventElapsedTime(ms, h->pev[0], h->pev[1]));
+    return AWE_OK;
+}
+
+// ---- reference generator ---------------------------------------------------------------------
+// the grids of a table over `coef`, or why not
+static int ref_grids(int n_k, int d, double period, const int* pieces, const int* degree, const double* brk,
+                     const double* coef, awe::RefArgs& a) {
+    if (n_k < 1 || d < 1) return fail(AWE_ERR_ARG, "n_k and d must be >= 1");
+    if (const char* why = awe::ref_check(pieces, degree, brk, period)) return fail(AWE_ERR_ARG, why);
+    const int channels[awe::kRefGrids] = {K3_NX, K3_NZ, K3_NU + K3_NX + K3_NZ};
+    int b0 = 0;
+    size_t c0 = 0;
+    for (int g = 0; g < awe::kRefGrids; ++g) {
+        a.g[g] = awe::RefGrid{b0, pieces[g], degree[g], channels[g], coef ? coef + c0 : nullptr};
+        b0 += pieces[g] + 1;
+        c0 += (size_t)pieces[g] * channels[g] * (degree[g] + 1);
+    }
+    a.period = period;
+    a.n_k = n_k, a.d = d, a.n_head = K3_NTH + K3_NPHI + K3_NXI, a.nx = K3_NX, a.nu = K3_NU, a.nz = K3_NZ;
+    return AWE_OK;
+}
+
+static size_t ref_ncoef(const awe::RefArgs& a) {
+    size_t n = 0;
+    for (const awe::RefGrid& g : a.g) n += (size_t)g.pieces * g.channels * (g.degree + 1);
+    return n;
+}
+
+int awempc_ref_set(awempc_handle h, double period, const double* offs, const double* head, const int* pieces,
+                   const int* degree, const double* brk, const double* coef) {
+    if (!h) return fail(AWE_ERR_ARG, "null handle");
+    if (!offs || !head || !coef) return fail(AWE_ERR_ARG, "null argument");
+    awe::RefArgs a{};
+    if (int rc = ref_grids(h->t.lay.n_k, h->t.lay.d, period, pieces, degree, brk, nullptr, a)) return rc;
+    h->ref_ready = false;
+    const int n_brk = a.g[2].brk0 + a.g[2].pieces + 1;
+    HIP_TRY(h->d_ref_brk.upload(brk, (size_t)n_brk));
+    HIP_TRY(h->d_ref_coef.upload(coef, ref_ncoef(a)));
+    HIP_TRY(h->d_ref_offs.upload(offs, (size_t)awe::ref_points(a.n_k, a.d)));
+    HIP_TRY(h->d_ref_head.upload(head, (size_t)a.n_head));
+    if (int rc = ref_grids(a.n_k, a.d, period, pieces, degree, brk, h->d_ref_coef, a)) return rc;
+    a.offs = h->d_ref_offs, a.head = h->d_ref_head, a.batch = h->batch;
+    h->ref = a;
+    h->ref_nbrk = n_brk;
+    h->ref_ready = true;
+    return AWE_OK;
+}
+
+int awempc_ref_window(awempc_handle h, const double* t0, double* out, size_t ld, size_t off, void* stream) {
+    if (!h) return fail(AWE_ERR_ARG, "null handle");
+    if (!h->ref_ready) return fail(AWE_ERR_ARG, "no reference tables: call awempc_ref_set first");
+    if (!t0 || !out) return fail(AWE_ERR_ARG, "null argument");
+    if (ld < off + (size_t)h->t.lay.n_v) return fail(AWE_ERR_ARG, "ld must be >= off + n_v");
+    hipStream_t s = (hipStream_t)stream;
+    awe::RefArgs a = h->ref;
+    a.t0 = t0, a.out = out, a.ld = ld, a.off = off;
+    const size_t n = (size_t)h->batch * (size_t)awe::ref_points(a.n_k, a.d);
+    HIP_TRY(hipEventRecord(h->rev[0], s));
+    mpc_ref_window_kernel<<<dim3((unsigned)((n + kRefBlock - 1) / kRefBlock)), kRefBlock, 0, s>>>(a, h->d_ref_brk,
+                                                                                                   h->ref_nbrk);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(h->rev[1], s));
+    h->rtimed = true;
+    return AWE_OK;
+}
+
+int awempc_ref_window_cpu(int n_k, int d, int batch, double period, const double* offs, const double* head,
+                          const int* pieces, const int* degree, const double* brk, const double* coef,
+                          const double* t0, double* out, size_t ld, size_t off) {
+    if (!offs || !head || !coef || !t0 || !out) return fail(AWE_ERR_ARG, "null argument");
+    if (batch < 1) return fail(AWE_ERR_ARG, "batch must be >= 1");
+    awe::RefArgs a{};
+    if (int rc = ref_grids(n_k, d, period, pieces, degree, brk, coef, a)) return rc;
+    const int n_v = a.n_head + n_k * (2 * K3_NX + K3_NU + K3_NZ + d * (K3_NX + K3_NZ)) + K3_NX;
+    if (ld < off + (size_t)n_v) return fail(AWE_ERR_ARG, "ld must be >= off + n_v");
+    a.offs = offs, a.head = head, a.batch = batch, a.t0 = t0, a.out = out, a.ld = ld, a.off = off;
+    const int n_pt = awe::ref_points(n_k, d);
+    for (int b = 0; b < batch; ++b)
+        for (int q = 0; q < n_pt; ++q) awe::ref_point(a, brk, (size_t)b, q);
+    return AWE_OK;
+}
+
+int awempc_last_ref_ms(awempc_handle h, float* ms) {
+    if (!h || !h->rtimed) return fail(AWE_ERR_ARG, "no timed reference window yet");
+    HIP_TRY(hipEventSynchronize(h->rev[1]));
+    if (ms) HIP_TRY(hipEventElapsedTime(ms, h->rev[0], h->rev[1]));
     return AWE_OK;
 }
 

@@ -18,7 +18,10 @@ step per sampling time for every loop, all loops batched:
   radau collocation (Newton on the shooting and collocation rows of interval 0, the interval's
   60 x 60 block of J_g) -- the collocation integrator of ``sim``; or by ``sim``'s default rk4root,
   as a host loop around the evaluator or fused into one kernel launch (``plant=``);
-* shift: the horizon moves one interval (the new last interval copies the old one).
+* shift: the horizon moves one interval (the new last interval copies the old one);
+* reference: the synthetic circle by default; the plant's own trajectory on the sampling grid
+  (``simulate_reference``); or, as Pmpc, any periodic trajectory of the model interpolated into every
+  horizon's window by one kernel launch (``track``, reference.py).
 
 The path inequalities (tether stress, acceleration) and variable bounds are not part of the
 step: along the tracked orbit they are inactive and the driver reports their maximum residual
@@ -185,6 +188,7 @@ class BatchedRti:
         self.plant, self.n_fe = plant, n_fe
         self.plant_tol = 1e-9                   # step(): plant_converged = residual <= plant_tol
         self.sim_blocks = self.sim_xs = None
+        self.track_tables = self.track_t0 = None
         # rk4root: the shooting-node rows of interval 0 against (xdot[0], z[0])
         rk_rows, rk_cols = lay.g_shooting(0), np.concatenate([lay.xdot(0), lay.z(0)])
         self.n_rk = len(rk_rows)
@@ -282,6 +286,7 @@ class BatchedRti:
         self.lam = torch.zeros(B, self.ne, dtype=torch.float64, device=self.dev)
         self.step_count = 0
         self.sim_blocks = self.sim_xs = None
+        self.track_tables = self.track_t0 = None
         self.t0_dev = torch.tensor(self.t0, dtype=torch.float64, device=self.dev)
         self._reference_setup()
         if self.hdiag is None:
@@ -326,6 +331,7 @@ class BatchedRti:
             x = x1
         xs[:, n_nodes] = x
         self.sim_blocks, self.sim_xs = blocks, xs
+        self.track_tables = self.track_t0 = None
         R = self._reference_sim(0)
         self.P[:, lay.p_ref:lay.p_ref + lay.n_v] = R
         self.P[:, lay.p_x0:lay.p_x0 + nx] = R[:, lay.x(0)[0]:lay.x(0)[0] + nx] + dx0
@@ -344,6 +350,50 @@ class BatchedRti:
         xN = lay.x(nk)[0]
         R[:, xN:xN + nx] = self.sim_xs[:, s + nk]
         return R
+
+    def track(self, traj, interpolator: str = "spline", t0=None):
+        """Track a periodic trajectory of the 3-DOF model (``reference.PeriodicTrajectory``), as the
+        reference's Pmpc tracks its optimised periodic solution: every window is that trajectory
+        interpolated at the horizon's times (``interpolator``: "spline" or "poly", pmpc.py:408-550),
+        taken modulo the period, so a loop may start at any time and never reaches an end.  Called
+        after ``start``; loop i's window starts at ``t0[i]`` (default: phases i T / B).  The current
+        perturbations of x0 and of the initial guess are kept relative to the new windows, as in
+        ``simulate_reference``; ``_shift`` then takes the window of t0 + (step_count + 1) ts from the
+        reference kernel (``MpcEvaluator.reference_window``: one launch for all loops, written into P
+        in place), or from its host twin with an evaluator that has none."""
+        lay, B = self.lay, self.B
+        nx, v0 = k3.NX, lay.v_intervals
+        tables = traj.tables(interpolator)
+        t0 = np.arange(B) * traj.T / B if t0 is None else np.asarray(t0, dtype=np.float64)
+        if t0.shape != (B,):
+            raise ValueError(f"t0 must be [{B}]")
+        if hasattr(self.ev, "reference_window"):
+            self.ev.set_reference(tables)
+        self.track_tables = tables
+        self.track_t0 = torch.tensor(t0, dtype=torch.float64, device=self.dev)
+        self.sim_blocks = self.sim_xs = None
+        ref_old = self.P[:, lay.p_ref:lay.p_ref + lay.n_v].clone()
+        x0s = slice(lay.x(0)[0], lay.x(0)[0] + nx)
+        dx0 = self.P[:, lay.p_x0:lay.p_x0 + nx] - ref_old[:, x0s]
+        dV = self.V - ref_old
+        V_save = self.V.clone()
+        self._reference_track(self.step_count)
+        R = self.P[:, lay.p_ref:lay.p_ref + lay.n_v]
+        self.P[:, lay.p_x0:lay.p_x0 + nx] = R[:, x0s] + dx0
+        self.V.copy_(R + dV)
+        self.V[:, :v0] = V_save[:, :v0]
+        self.V[:, self.fict] = V_save[:, self.fict]
+
+    def _reference_track(self, s: int):
+        """The tracked trajectory's windows starting at track_t0 + s ts, written into P's ``ref``."""
+        lay = self.lay
+        t = self.track_t0 + s * self.consts.cfg.ts
+        if hasattr(self.ev, "reference_window"):
+            self.ev.reference_window(t, out=self.P, ld=self.P.shape[1], off=lay.p_ref)
+        else:
+            from .mpc import reference_window_cpu
+            R = reference_window_cpu(self.track_tables, t.cpu().numpy(), lay, self.consts)
+            self.P[:, lay.p_ref:lay.p_ref + lay.n_v] = torch.as_tensor(R, device=self.dev)
 
     def _hessian_diagonal(self):
         """The tracking cost is quadratic and separable: grad(V + h) - grad(V) = h diag(H)."""
@@ -529,7 +579,13 @@ class BatchedRti:
         shifted = torch.cat([body[:, 1:], body[:, -1:]], dim=1).reshape(self.B, nk * st)
         self.V[:, v0:v0 + nk * st] = shifted
         self.P[:, lay.p_x0:lay.p_x0 + k3.NX] = x1
-        if self.sim_blocks is not None:
+        if self.track_tables is not None:
+            self._reference_track(self.step_count + 1)
+            # as below: the reference's tail is the guess of the new last interval and x[N]
+            tail = slice(v0 + (nk - 1) * st, lay.n_v)
+            self.V[:, tail] = self.P[:, lay.p_ref + tail.start:lay.p_ref + tail.stop]
+            self.V[:, self.fict] = 0.0
+        elif self.sim_blocks is not None:
             R = self._reference_sim(self.step_count + 1)
             self.P[:, lay.p_ref:lay.p_ref + lay.n_v] = R
             # the new last interval and x[N]: the reference's (a solution of the dynamics) instead of

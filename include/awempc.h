@@ -128,6 +128,33 @@ int awempc_plant_rk4root_cpu(const double* consts, int n_consts, int batch, cons
 /* kernel time of the last awempc_plant_rk4root (HIP events on its stream), ms */
 int awempc_last_plant_ms(awempc_handle h, float* ms);
 
+/* ---- the reference generator ------------------------------------------------------------------
+ * Pmpc's reference windows (pmpc.py:408-550: get_reference on the interpolated periodic solution): a
+ * periodic trajectory, given as piecewise polynomials, evaluated at every time of a loop's horizon
+ * (reduced as t - T floor(t / T)) and written as the loop's V-shaped window.  One launch for all loops,
+ * one thread per (loop, time point).
+ * A table is three grids, in this order: the states (K3_NX channels), the algebraic variables (K3_NZ)
+ * and what an interval holds (K3_NU + K3_NX + K3_NZ: u, then the shooting node's xdot and z).  Grid g
+ * has pieces[g] pieces of degree[g]; brk = the grids' breakpoints one after another (pieces[g] + 1
+ * each, strictly ascending from 0 to the period), coef = their coefficients one after another,
+ * [piece][channel][degree + 1] in s = (t - b_i) / (b_{i+1} - b_i), lowest power first.
+ * offs[(n_k + 1) + n_k d + n_k]: the time offsets of the shooting, collocation (interval-major) and
+ * control points from the window's start; head[K3_NTH + K3_NPHI + K3_NXI]: theta, phi, xi as written.
+ * awempc_ref_set refuses (awempc_last_error() says why) a degree above 7 or more than 2048 breakpoints
+ * in all: what the kernel's LDS staging holds.  The handle keeps its own device copy of the table.
+ * awempc_ref_window: t0[B] and out are device pointers, out[b * ld + off + i] for i < n_v (ld = n_p,
+ * off = n_x writes the `ref` entry of p in place); asynchronous on `stream`.  A NaN or infinite t0[b]
+ * gives loop b a non-finite window and touches nothing else. */
+int awempc_ref_set(awempc_handle h, double period, const double* offs, const double* head, const int* pieces,
+                   const int* degree, const double* brk, const double* coef);
+int awempc_ref_window(awempc_handle h, const double* t0, double* out, size_t ld, size_t off, void* stream);
+/* the same core on the host, no device and no handle: host pointers */
+int awempc_ref_window_cpu(int n_k, int d, int batch, double period, const double* offs, const double* head,
+                          const int* pieces, const int* degree, const double* brk, const double* coef,
+                          const double* t0, double* out, size_t ld, size_t off);
+/* kernel time of the last awempc_ref_window (HIP events on its stream), ms */
+int awempc_last_ref_ms(awempc_handle h, float* ms);
+
 /* ---- nlp_hess_l ----------------------------------------------------------------------------------
  * Hessian of sigma f + lam^T g w.r.t. V, upper triangle (row <= col), CCS over the n_v columns:
  * H[b*nnz_h + i].  sigma[b], lam[b*n_g + i].  The structure is derived on the host from the node

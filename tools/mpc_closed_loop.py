@@ -2,6 +2,7 @@
 (awebox_amd/rti.py), with a per-phase time breakdown (linearisation + KKT solve, plant, shift).
 
     python tools/mpc_closed_loop.py --batch 256 --steps 40 --out gpurun_out/mpc_rti.json
+    python tools/mpc_closed_loop.py --reference cycle.npz --interpolator spline     # track a periodic trajectory
 """
 import argparse
 import json
@@ -20,6 +21,9 @@ def main():
     ap.add_argument("--d", type=int, default=4)
     ap.add_argument("--out", default=None)
     ap.add_argument("--plant", choices=["collocation", "rk4root", "rk4root_fused"], default="collocation")
+    ap.add_argument("--reference", default=None, metavar="FILE.npz",
+                    help="track this periodic trajectory (reference.PeriodicTrajectory.save) instead of the circle")
+    ap.add_argument("--interpolator", choices=["poly", "spline"], default="spline")
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -30,6 +34,12 @@ def main():
     c = k3.build_constants(k3.Kite3Config(n_k=a.n_k, d=a.d))
     r = BatchedRti(c, a.batch, device="cuda", plant=a.plant)
     r.start()
+    if a.reference:
+        from awebox_amd.reference import PeriodicTrajectory
+        traj = PeriodicTrajectory.load(a.reference)
+        print(json.dumps({"reference": a.reference, "period": traj.T, "n_k": traj.n_k, "d": traj.d,
+                          "closure_gap": traj.closure_gap, "interpolator": a.interpolator}), flush=True)
+        r.track(traj, a.interpolator)
     sync = torch.cuda.synchronize
     phases = {"iterate": [], "plant": [], "shift": []}
     hist = []
