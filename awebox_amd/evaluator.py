@@ -179,10 +179,10 @@ class Ap2Evaluator(nb.NlpEvaluator):
 
     # ---------------------------------------------- timers -----------------------------
     def last_kernel_ms_soa(self):
-        """HIP-event times of the last instance-minor call (ms): input transpose; the Radau kernel
-        (node code and its workgroups' interval pass) with the shooting kernel beside it on a second
-        stream; the wait for that stream's join after the Radau kernel (there is no separate interval
-        kernel); finalize; output transpose."""
+        """HIP-event times of the last instance-minor call (ms): input transpose (0 with
+        instance-minor inputs); the node launch (shooting and Radau tiles, the Radau workgroups'
+        interval pass); the finalize kernel; 0 (once the finalize kernel's slot: there is no
+        separate interval kernel); output transpose (0 with instance-minor outputs)."""
         ms = (ctypes.c_float * 5)()
         self._call("last_kernel_ms_soa", ms)
         return [float(x) for x in ms]

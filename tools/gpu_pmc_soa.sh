@@ -1,5 +1,5 @@
 #!/bin/bash
-# PMC passes over the instance-minor evaluation path (ap2_soa_shoot / radau, finalize,
+# PMC passes over the instance-minor evaluation path (ap2_soa_eval, finalize,
 # B=2048, tools/pmc_kernels.py --ap2): HBM bytes (FETCH_SIZE, WRITE_SIZE), instruction mix,
 # wave-state cycles, one counter group per run with the kernel trace only; then the kernel-trace
 # statistics of the same program.

@@ -106,7 +106,7 @@ def record_gen(batch, dirs):
     print("wrote profiles/pmc_traffic.json", json.dumps({k: v for k, v in tot.items()}))
 
 
-SOA_KERNELS = ("ap2_soa_in_kernel", "ap2_soa_shoot_kernel", "ap2_soa_radau_kernel",
+SOA_KERNELS = ("ap2_soa_in_kernel", "ap2_soa_eval_kernel",
                "ap2_finalize_kernel")   # ap2_soa_in_kernel only runs with per-instance inputs
 
 
