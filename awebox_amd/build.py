@@ -11,6 +11,7 @@ travel with the repository snapshot to the GPU box.
 Before the libraries are compiled, ``generate()`` refreshes the generated node code: each node model
 is traced and differentiated by its generator under ``csrc/gen/`` (g++, host) for the default
 constants -- ``ap2_nodejac.gen.hpp`` / ``ap2_nodehess.gen.hpp`` (AP2 Jacobian and Hessian),
+``ap2_noderoot.gen.hpp`` (the AP2 re-integrator's rootfinder),
 ``kite3_nodejac.gen.hpp`` (tracking MPC), ``kite3_noderoot.gen.hpp`` (its plant's rootfinder),
 ``dual_nodejac.gen.hpp`` (dual kites) -- and the straight-line code they write is what the
 instance-minor kernels run.
@@ -35,6 +36,11 @@ GEN_SOURCES = [os.path.join(CSRC, "gen", f) for f in ("ap2_jacgen.cpp", "sym.hpp
 # the node-Hessian code (forward-over-reverse, csrc/gen/ap2_hessgen.cpp)
 HESS_HEADER = os.path.join(CSRC, "ap2_nodehess.gen.hpp")
 HESS_SOURCES = [os.path.join(CSRC, "gen", "ap2_hessgen.cpp")] + GEN_SOURCES[1:]
+# the AP2 re-integrator's rootfinder node code (csrc/gen/ap2_rootgen.cpp): the model, not the NLP's tables
+AP2_ROOT_HEADER = os.path.join(CSRC, "ap2_noderoot.gen.hpp")
+AP2_ROOT_SOURCES = [os.path.join(CSRC, "gen", f) for f in ("ap2_rootgen.cpp", "sym.hpp")] + [
+    os.path.join(CSRC, f) for f in ("ap2_model.hpp", "scalar.hpp")] + [
+    os.path.join(INCLUDE, "awegpu.h"), os.path.join(HERE, "problem.py")]
 # the tracking-MPC node-Jacobian code (csrc/gen/kite3_jacgen.cpp)
 K3_HEADER = os.path.join(CSRC, "kite3_nodejac.gen.hpp")
 K3_SOURCES = [os.path.join(CSRC, "gen", f) for f in ("kite3_jacgen.cpp", "sym.hpp")] + [
@@ -51,6 +57,7 @@ DUAL_SOURCES = [os.path.join(CSRC, "gen", f) for f in ("dual_jacgen.cpp", "sym.h
     os.path.join(INCLUDE, "awedual.h"), os.path.join(INCLUDE, "awegpu.h"), os.path.join(HERE, "dual.py")]
 # (header, generator source, inputs hashed into the header's first line, default constants)
 GENERATORS = [(GEN_HEADER, "ap2_jacgen.cpp", GEN_SOURCES, "ap2"), (HESS_HEADER, "ap2_hessgen.cpp", HESS_SOURCES, "ap2"),
+              (AP2_ROOT_HEADER, "ap2_rootgen.cpp", AP2_ROOT_SOURCES, "ap2"),
               (K3_HEADER, "kite3_jacgen.cpp", K3_SOURCES, "kite3"),
               (K3_ROOT_HEADER, "kite3_rootgen.cpp", K3_ROOT_SOURCES, "kite3"), (DUAL_HEADER, "dual_jacgen.cpp", DUAL_SOURCES, "dual")]
 # content hash of GEN_SOURCES recorded in the generated header's first line: the header is stale
@@ -60,7 +67,9 @@ _COMMON = [os.path.join(CSRC, f) for f in ("ap2_model.hpp", "ap2_tables.hpp", "s
                                            "im_layout.hpp", "im_tables.hpp")] + [
     os.path.join(INCLUDE, "awegpu.h")]
 TARGETS = {
-    LIB: ([os.path.join(CSRC, "awegpu.hip")], _COMMON + [GEN_HEADER, HESS_HEADER]),
+    LIB: ([os.path.join(CSRC, "awegpu.hip")],
+          _COMMON + [os.path.join(CSRC, "plant_rk4root.hpp"), os.path.join(INCLUDE, "awegpu_rk4root.h"),
+                     GEN_HEADER, HESS_HEADER, AP2_ROOT_HEADER]),
     LIB_MPC: ([os.path.join(CSRC, "awempc.hip")],
               _COMMON + [os.path.join(CSRC, f) for f in ("kite3_model.hpp", "kite3_tables.hpp",
                                                          "plant_rk4root.hpp", "ref_pp.hpp")]

@@ -879,6 +879,8 @@ struct K3PlantNode {
                 if (awe_k3root::kSlot[r][j] < 0) sys.a(r, j) = 0.0;      // the LU fills in: rewritten every time
         awe_k3root::k3_node_root<1>(PlantIn{x, y, u, par}, par[3], cst, PlantRows<Sys>{sys}, PlantSlots<Sys>{sys});
     }
+    template <class Sys>
+    AWE_HD void solve(Sys& sys, double* y) const { awe::rk4root_solve_update<kPlantN>(sys, y); }
     // the power integral's integrand lambda l_t dl_t in SI units (dynamics.py:318-330)
     AWE_HD double integrand(int, const double* x, const double* y) const {
         const double* s = cst + K3_C_SCALING;

@@ -10,9 +10,13 @@
 //     void begin(int step)                            the sampling time's control becomes the applied one;
 //     void eval(int step, const double* x, const double* y, Sys& sys) const
 //         rows sys.r(i) and the dense block sys.a(i, j) = d row_i / d y_j at (x, y), control of `step`;
-//     double integrand(int step, const double* x, const double* y) const     the quadrature's integrand;
+//     void solve(Sys& sys, double* y) const           one Newton step y -= A^-1 r from what eval left in sys: a
+//         dense node calls rk4root_solve_update<NUNK>; a node whose rows partly hold one unknown alone (the
+//         AP2 kite: 17 of 24) solves those in closed form and hands rk4root_lu_solve<K> the K x K rest;
+//     double integrand(int step, const double* x, const double* y) const     the quadrature's integrand at
+//         the (x, y) of the rootfinder call before it;
 //     double rate(int i, double ydot_i) const         dx_i / dt [1/s] from y_i (the scaling ratio);
-// and `Sys` holds the NUNK x NUNK matrix and right-hand side of the instance wherever its owner keeps them
+// and `Sys` holds the matrix and the NUNK-row right-hand side of the instance wherever its owner keeps them
 // (the kernel: LDS, lane-minor; the host: a plain array), through r(i) and a(i, j) returning references.
 //
 // Every loop's trip count is an argument or a constant: no loop waits on convergence.  A comparison with
@@ -68,8 +72,16 @@ AWE_HD void rk4root_lu_solve(Sys& sys) {
     }
 }
 
+// The dense Newton step: y -= A^-1 r with all NUNK rows in the LU.
+template <int NUNK, class Sys>
+AWE_HD void rk4root_solve_update(Sys& sys, double* y) {
+    rk4root_lu_solve<NUNK>(sys);
+#pragma unroll
+    for (int i = 0; i < NUNK; ++i) y[i] -= sys.r(i);
+}
+
 // Newton on the node rows for y at the state x: evaluate, res = max |row|, stop when res < tol or after
-// max_newton solves, otherwise y -= A^-1 r.  Returns res at exit.
+// max_newton solves, otherwise node.solve (y -= A^-1 r).  Returns res at exit.
 template <int NUNK, class Node, class Sys>
 AWE_HD double rk4root_find(const Node& node, int step, const double* x, double* y, Sys& sys, int max_newton,
                            double tol) {
@@ -87,9 +99,7 @@ AWE_HD double rk4root_find(const Node& node, int step, const double* x, double* 
         }
         if (nan) res = __builtin_nan("");
         if (res < tol || it == max_newton) break;
-        rk4root_lu_solve<NUNK>(sys);
-#pragma unroll
-        for (int i = 0; i < NUNK; ++i) y[i] -= sys.r(i);
+        node.solve(sys, y);
     }
     return res;
 }

@@ -42,12 +42,24 @@ SIGNATURES = {
     "last_kernel_ms_soa": [H, FP],
 }
 EXPORTED_SYMBOLS = nb.exported(PREFIX, SIGNATURES)
+# the rk4root re-integration, declared in include/awegpu_rk4root.h beside awegpu.h
+RK4ROOT_SIGNATURES = {
+    "integrate_rk4root": [H, I] + [VP] * 5 + [I, I, I, ctypes.c_double] + [VP] * 5,
+    "integrate_rk4root_cpu": [nb.DP, I, I] + [nb.DP] * 5 + [I, I, I, ctypes.c_double] + [nb.DP] * 4,
+    "rk4root_par_layout": [IP, IP],
+    "last_integrate_ms": [H, FP],
+}
+RK4ROOT_SYMBOLS = [PREFIX + name for name in RK4ROOT_SIGNATURES]
 
 PATH_COLOUR, PATH_GENERATED, PATH_SOA = 0, 1, 2
 
 
 def load_library(path: str = _LIB_PATH):
-    return nb.load(path, PREFIX, SIGNATURES)
+    lib = nb.load(path, PREFIX, SIGNATURES)
+    for name, sig in RK4ROOT_SIGNATURES.items():
+        fn = getattr(lib, PREFIX + name)
+        fn.argtypes, fn.restype = sig, I
+    return lib
 
 
 def _n_v(consts):
@@ -62,6 +74,62 @@ def sparsity_jac_static(consts: pb.Ap2Constants):
 def sparsity_hess_static(consts: pb.Ap2Constants):
     """Upper-triangular CCS pattern (colind, row) of nlp_hess_l derived on the CPU."""
     return nb.static_sparsity(load_library(), PREFIX, "hess", consts, _n_v(consts))
+
+
+RK_NUNK = pb.NX + pb.NZ      # the rootfinder's unknowns y = (xdot, z)
+
+
+def rk4root_par_layout():
+    """Sources of a task's parameter row (awe_rk4root_par_layout, include/awegpu_rk4root.h): entry < 1000 is
+    node variable i (57 theta.diam_t, 58 theta.t_f, 59 phi.gamma), entry >= 1000 theta0 entry i - 1000."""
+    lib = load_library()
+    n = ctypes.c_int()
+    lib.awe_rk4root_par_layout(ctypes.byref(n), None)
+    src = np.zeros(n.value, dtype=np.int32)
+    lib.awe_rk4root_par_layout(ctypes.byref(n), nb._iptr(src))
+    return src
+
+
+def rk4root_par(theta, gamma, theta0):
+    """Parameter rows [n, n_par] of n integration tasks from theta [n, 2] (scaled diam_t, t_f), phi.gamma
+    [n] and theta0 [n, NTHETA0] (P's tail): numpy arrays or torch tensors, the result of the same kind."""
+    src = rk4root_par_layout()
+    node = np.concatenate([theta, gamma[:, None]], axis=1) if isinstance(theta, np.ndarray) else None
+    if node is None:
+        import torch
+        node = torch.cat([theta, gamma[:, None]], dim=1)
+        cat = lambda a, b: torch.cat([a, b], dim=1)   # noqa: E731
+    else:
+        cat = lambda a, b: np.concatenate([a, b], axis=1)   # noqa: E731
+    n_in = int((src < 1000).sum())
+    return cat(node[:, (src[:n_in] - pb.W_TH0).tolist()], theta0[:, (src[n_in:] - 1000).tolist()])
+
+
+def _rk4root_shapes(n, n_steps):
+    return ((n, pb.NX), (n, n_steps, pb.NU), (n, RK_NUNK), (n, len(rk4root_par_layout())), (n,))
+
+
+def integrate_rk4root_cpu(consts, x0, u, y0, par, ts, n_fe, n_steps=1, max_newton=20, tol=1e-12):
+    """``Ap2Evaluator.integrate_rk4root`` on the host, no device: ``consts`` are the model constants
+    (``Ap2Constants`` or their vector); numpy arrays x0 [n, 23], u [n, n_steps, 10], y0 [n, 24], par
+    [n, n_par] (``rk4root_par``), ts [n].  Returns dict(xf [n, n_steps, 23], yf [n, 24], qf [n, n_steps],
+    res [n])."""
+    lib = load_library()
+    c = np.ascontiguousarray(getattr(consts, "consts", consts), dtype=np.float64)
+    arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in (x0, u, y0, par, ts)]
+    n = arrs[0].shape[0] if arrs[0].ndim == 2 else 0
+    if n >= 1 and n_steps >= 1:
+        for a, shape in zip(arrs, _rk4root_shapes(n, n_steps)):
+            if a.shape != shape:
+                raise ValueError(f"expected an array of shape {shape}, got {a.shape}")
+    n, m = max(n, 0), max(n_steps, 0)
+    out = {"xf": np.zeros((n, m, pb.NX)), "yf": np.zeros((n, RK_NUNK)), "qf": np.zeros((n, m)), "res": np.zeros(n)}
+    rc = lib.awe_integrate_rk4root_cpu(nb._dptr(c), c.size, arrs[0].shape[0] if arrs[0].ndim == 2 else 0,
+                                       *(nb._dptr(a) for a in arrs), int(n_fe), int(n_steps), int(max_newton),
+                                       float(tol), *(nb._dptr(a) for a in out.values()))
+    if rc != AWE_OK:
+        raise AwegpuError(f"awegpu error {rc}: {nb.last_error(lib, PREFIX)}")
+    return out
 
 
 class Ap2Evaluator(nb.NlpEvaluator):
@@ -131,6 +199,35 @@ class Ap2Evaluator(nb.NlpEvaluator):
             raise ValueError("H must be an instance-minor [batch, nnz_h] float64 view (strides (1, ld))")
         self._call("eval_hess_im", V.data_ptr(), P.data_ptr(), sigma.data_ptr(), lam_g.data_ptr(), H.data_ptr(),
                    int(H.stride(1)), self._stream(stream))
+
+    # ---------------------------------------------- rk4root re-integration -------------
+    def integrate_rk4root(self, x0, u, y0, par, ts, n_fe, n_steps=1, max_newton=20, tol=1e-12, stream=None):
+        """The reference's rk4root (tools/integrator_routines.py:32-96) for n integration tasks in one
+        launch, one lane per task (n is free: it is not the evaluator's batch): ``n_steps`` sampling
+        times of length ts[t] [s], ``n_fe`` RK4 steps each, the control u[t, s] held over sampling time s,
+        a Newton rootfinder for y = (xdot, z) at every stage and at the end of every sampling time.
+        Contiguous float64 CUDA tensors x0 [n, 23], u [n, n_steps, 10] (scaled), y0 [n, 24] (the
+        rootfinder's guess), par [n, n_par] (``rk4root_par``), ts [n].  Returns (xf [n, n_steps, 23],
+        yf [n, 24] at the last xf, qf [n, n_steps] energy of each sampling time [J], res [n] the largest
+        rootfinder residual)."""
+        import torch
+        n = x0.shape[0] if x0.dim() == 2 else 0
+        for t, shape in zip((x0, u, y0, par, ts), _rk4root_shapes(n, max(n_steps, 0))):
+            if t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != shape:
+                raise ValueError(f"expected a contiguous float64 CUDA tensor of shape {shape}")
+        f64 = dict(dtype=torch.float64, device=x0.device)
+        xf, yf = torch.empty(n, max(n_steps, 0), pb.NX, **f64), torch.empty(n, RK_NUNK, **f64)
+        qf, res = torch.empty(n, max(n_steps, 0), **f64), torch.empty(n, **f64)
+        self._call("integrate_rk4root", n, x0.data_ptr(), u.data_ptr(), y0.data_ptr(), par.data_ptr(), ts.data_ptr(),
+                   int(n_fe), int(n_steps), int(max_newton), float(tol), xf.data_ptr(), yf.data_ptr(), qf.data_ptr(),
+                   res.data_ptr(), self._stream(stream))
+        return xf, yf, qf, res
+
+    def last_integrate_ms(self):
+        """Kernel time of the last ``integrate_rk4root`` (HIP events), ms."""
+        a, = nb._floats(1)
+        self._call("last_integrate_ms", ctypes.byref(a))
+        return a.value
 
     # ---------------------------------------------- kernel selection -------------------
     HESS_PATHS = {"hyperdual": 0, "generated": 1, "follow": 2}

@@ -23,6 +23,11 @@ integrators here solve exactly those rows with the HIP evaluator's values and Ja
 All arithmetic is float64 on the evaluator's device; the small Newton systems (24 and 120 unknowns
 for the AP2 kite) are dense solves.  ``integrand(x, z)`` returns the quadrature integrand per
 instance from scaled states x [B, n_x] and algebraic variables z [B, n_z].
+
+``IntervalIntegrator`` is the host loop: every Newton iteration of every stage evaluates the whole NLP.
+``reintegrate`` and ``simulate_open_loop`` run rk4root fused instead -- one lane per (instance, interval)
+or per instance, the whole integrator in one launch (``Ap2Evaluator.integrate_rk4root``) -- and are held to
+``IntervalIntegrator.rk4root`` by the tests.
 """
 from __future__ import annotations
 
@@ -155,3 +160,98 @@ class IntervalIntegrator:
         ode(x)
         z_end = Vp[:, self.z_idx]
         return {"x_end": x, "z_end": z_end, "q": q, "residual": worst}
+
+
+# ---- the fused rk4root: one lane per integration task (csrc/plant_rk4root.hpp on the generated node code) ----
+def _as_torch(a, dev):
+    return (a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a), dtype=torch.float64)).to(
+        device=dev, dtype=torch.float64)
+
+
+def _run_rk4root(ev, consts, x0, u, y0, par, ts, n_fe, n_steps, max_newton, tol, device):
+    """Both back ends behind one call on torch tensors: the kernel (``ev.integrate_rk4root``) on a CUDA
+    device, the host core (``evaluator.integrate_rk4root_cpu``) with ``device="cpu"`` (``ev`` unused)."""
+    args = [t.contiguous() for t in (x0, u, y0, par, ts)]
+    if torch.device(device).type == "cpu":
+        from .evaluator import integrate_rk4root_cpu
+        o = integrate_rk4root_cpu(consts, *(t.numpy() for t in args), n_fe, n_steps, max_newton, tol)
+        return tuple(torch.from_numpy(o[k]) for k in ("xf", "yf", "qf", "res"))
+    return ev.integrate_rk4root(*args, n_fe, n_steps, max_newton, tol)
+
+
+def reintegrate(ev, lay, consts, V, P, n_fe=30, device="cuda", max_newton=20, tol=1e-12):
+    """The reference's rk4root check of a direct-collocation solution (test/reg/test_discretization.py:
+    20-193) over ALL n_k intervals of every instance of V [B, n_v], P [B, n_p] in one launch: task
+    (b, k) starts at x0 = V.x[k] with the control V.u[k] held, the rootfinder's guess (V.xdot[k], V.z[k])
+    and takes n_fe RK4 steps over the interval t_f / n_k.  Returns a dict of [B, n_k] tensors: the three
+    relative errors test_discretization.error defines, max |found - expected| / max |expected|, of
+
+    * ``x``: the end state against V.x[k+1],
+    * ``z``: the end algebraic variable against V.coll_z[k, d-1],
+    * ``q``: the interval's energy against ``homotopy.interval_energy(k)``,
+
+    the largest rootfinder ``residual``, and what was found: ``x_end`` [B, n_k, 23], ``z_end`` [B, n_k, 1],
+    ``q_end`` [B, n_k].  ``device="cpu"`` runs the host core (``ev`` may then be None)."""
+    from . import problem as pb
+    from .evaluator import rk4root_par
+    dev = torch.device(device)
+    V, P = _as_torch(V, dev), _as_torch(P, dev)
+    if V.dim() == 1:
+        V, P = V[None], P[None]
+    B, n_k, d = V.shape[0], lay.n_k, lay.d
+    idx = lambda f: torch.as_tensor(np.stack([f(k) for k in range(n_k)]), device=dev)   # noqa: E731
+    rows = lambda i: V[:, i].reshape(B * n_k, -1)                                       # noqa: E731
+    x0, u = rows(idx(lay.x)), rows(idx(lay.u))
+    y0 = torch.cat([rows(idx(lay.xdot)), rows(idx(lay.z))], dim=1)
+    per_task = lambda a: a.repeat_interleave(n_k, dim=0)                                # noqa: E731
+    th = V[:, torch.as_tensor(lay.theta(), device=dev)]
+    par = rk4root_par(per_task(th), per_task(V[:, int(lay.phi("gamma"))]),
+                      per_task(P[:, lay.p_theta0:lay.p_theta0 + pb.NTHETA0]))
+    s = torch.as_tensor(np.asarray(consts.scaling), device=dev)
+    t_f = th[:, 1] * s[pb.W_TH0 + 1]
+    xf, yf, qf, res = _run_rk4root(ev, consts, x0, u.reshape(B * n_k, 1, pb.NU), y0, par, per_task(t_f / n_k),
+                                   n_fe, 1, max_newton, tol, dev)
+    x_end, z_end, q_end = xf.reshape(B, n_k, pb.NX), yf[:, pb.NX:].reshape(B, n_k, pb.NZ), qf.reshape(B, n_k)
+    x_exp = V[:, idx(lambda k: lay.x(k + 1))]
+    z_exp = V[:, idx(lambda k: lay.coll_z(k, d - 1))]
+    # homotopy.interval_energy for every (instance, interval)
+    w = torch.as_tensor(np.asarray(pb.collocation(d)[3], dtype=float), device=dev)
+    o_l, o_dl, o_lam = pb.W_OFF[("x", "l_t")][0], pb.W_OFF[("x", "dl_t")][0], pb.W_OFF[("z", "lambda10")][0]
+    q_exp = torch.zeros(B, n_k, dtype=torch.float64, device=dev)
+    for j in range(d):
+        cx = V[:, idx(lambda k: lay.coll_x(k, j))]
+        lam = V[:, idx(lambda k: lay.coll_z(k, j))][..., 0]
+        q_exp = q_exp + (t_f / n_k)[:, None] * w[j] * lam * s[o_lam] * cx[..., o_l] * s[o_l] * cx[..., o_dl] * s[o_dl]
+    rel = lambda a, b: (a - b).abs().amax(dim=-1) / b.abs().amax(dim=-1)                # noqa: E731
+    return {"x": rel(x_end, x_exp), "z": rel(z_end, z_exp), "q": (q_end - q_exp).abs() / q_exp.abs(),
+            "residual": res.reshape(B, n_k), "x_end": x_end, "z_end": z_end, "q_end": q_end}
+
+
+def simulate_open_loop(ev, consts, x0, u_seq, ts, n_fe=20, y0=None, theta=None, gamma=None, theta0=None,
+                       max_newton=20, tol=1e-12, device="cuda"):
+    """The reference's open-loop simulation (sim.py:72-78, 'open_loop': the integrator run forward on the
+    trial's model under given controls) of the 6-DOF kite for B instances and ``n_steps =
+    u_seq.shape[1]`` sampling times in one launch, without the host in the loop: x0 [B, 23] and u_seq
+    [B, n_steps, 10] scaled, ts the length of a sampling time [s] (a number or [B]).  y0 [B, 24] is the
+    rootfinder's first guess for (xdot, z) (default: xdot = 0, lambda = 1 scaled); theta [B, 2] (default: the
+    fixed diameter), gamma [B] (default 0: no fictitious forces) and theta0 [B, NTHETA0] (default: the
+    constants' own) complete the model.  Returns dict(x [B, n_steps, 23], y [B, 24] at the last state,
+    q [B, n_steps] energy per sampling time [J], residual [B])."""
+    from . import problem as pb
+    from .evaluator import RK_NUNK, rk4root_par
+    dev = torch.device(device)
+    x0, u_seq = _as_torch(x0, dev), _as_torch(u_seq, dev)
+    B, n_steps = x0.shape[0], u_seq.shape[1]
+    f64 = dict(dtype=torch.float64, device=dev)
+    if y0 is None:
+        y0 = torch.zeros(B, RK_NUNK, **f64)
+        y0[:, pb.NX:] = 1.0
+    if theta is None:
+        theta = torch.tensor([consts.cfg.diam_t_fixed / consts.scaling[pb.W_TH0], 0.0], **f64).expand(B, 2)
+    gamma = torch.zeros(B, **f64) if gamma is None else _as_torch(gamma, dev)
+    theta0 = torch.as_tensor(consts.theta0, **f64).expand(B, pb.NTHETA0) if theta0 is None else _as_torch(theta0, dev)
+    ts = torch.as_tensor(ts, **f64).expand(B) if not isinstance(ts, torch.Tensor) or ts.dim() == 0 else ts.to(**f64)
+    par = rk4root_par(_as_torch(theta, dev), gamma, theta0)
+    xf, yf, qf, res = _run_rk4root(ev, consts, x0, u_seq, _as_torch(y0, dev), par, ts, n_fe, n_steps, max_newton,
+                                   tol, dev)
+    return {"x": xf, "y": yf, "q": qf, "residual": res}
