@@ -5,7 +5,9 @@ MI355X.
   and of the whole objective) through the committed fixtures tests/golden/dual_hess_*.npz
   (tests/golden/make_dual_hess_golden.py): |a - b| <= 1e-9 |b| + 1e-11 max|H|, the fp64 tolerance
   of the AP2 Hessian parity test (test_gpu_parity.py).  psi is set strictly inside (0, 1) so the
-  tracking and the period-coupled power cost both contribute.
+  tracking and the period-coupled power cost both contribute.  dual_hess_full_p_n3_d2 has every entry
+  of P moved (tests/param_cases.dual_full_p): the t_f cost split over the two t_f, theta regularisation
+  and distinct weights and costs are in its Hessian.
 * Config 3 at its full size (N=60, d=4): agreement with the coloured central differences of the
   exact HIP gradient (fd_hessian.py), |H_fd - H| <= 1e-6 max|column| + 1e-9 max|H|, which is the
   size-independent check available where the oracle is too slow; plus batch invariance and
@@ -46,7 +48,7 @@ def _fixture(name):
     return mc, lay, z, Ho
 
 
-@pytest.mark.parametrize("name", ["dual_hess_n3_d2", "dual_hess_n4_d3"])
+@pytest.mark.parametrize("name", ["dual_hess_n3_d2", "dual_hess_n4_d3", "dual_hess_full_p_n3_d2"])
 def test_dual_hessian_matches_oracle(gpu, name):
     from awebox_amd.dual_evaluator import DualEvaluator
     mc, lay, z, Ho = _fixture(name)
